@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """FITC nLML + hyper-gradient throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
         ONE process for any N -- the reference's launch shape (bin/ocaml_gpr.ml is one process): with N > 1 the N devices
         are reached through the C ABI's own multi-device entry, gprhip_ctx_create(devices[]) -> gprhip_sharded_eval
         (row shards, one worker thread per device and the RCCL all-reduces inside libgprhip.so).
@@ -17,9 +17,14 @@ region) and the training inputs already resident in HBM.  With N > 1 the n train
 devices (strong scaling of the same n) with two RCCL all-reduces per step.
 Rank 0 prints ONE JSON line.
 
-The timed region carries one HIP-event pair per step (around the dominant kernel, on the library's own stream);
-the per-stage times (`stage_ms`), the evidence-only rate, the collective times and the other BASELINE configurations
-(`configs`) are measured in separate passes after it.
+The timed region carries one HIP-event pair per step (around the dominant kernel, on the library's own stream).
+A plain run sets up, warms up, times the K steps and prints the line.  With --full the per-stage times (`stage_ms`,
+`roofline_k_builder`, `roofline_job.mfma_engine_ms_per_step`), the evidence-only rate, the collective times
+(`multi_gpu`), the single-process context entry, the other BASELINE configurations (`configs`) and the CPU baseline
+are measured as well, in separate passes after it (--no-configs / --no-cpu-baseline leave out the last three).
+
+--dump-outputs DIR writes what the last timed step returned (l1, l2, l, dl_dsigma2, the gradient and the mean
+coefficients) as DIR/<name>.npy in float64; the inputs depend only on the arguments, so two builds can be compared.
 """
 import argparse
 import glob
@@ -46,6 +51,15 @@ def synth(seed, n, m, d):
     y = np.sin(X.sum(0)) + 0.1 * rng.normal(size=n)
     Z = X[:, rng.permutation(n)[:m]] + 0.01 * rng.normal(size=(d, m))
     return np.asfortranarray(X), y, np.asfortranarray(Z)
+
+
+def dump_outputs(path, ev):
+    """What a caller of the timed path receives from its last step, one float64 .npy per field (~150 KB at the
+    headline shape)."""
+    os.makedirs(path, exist_ok=True)
+    for name, val in (("l1", ev.l1), ("l2", ev.l2), ("l", ev.l), ("dl_dsigma2", ev.dl_dsigma2), ("grad", ev.grad),
+                      ("coeffs", ev.coeffs)):
+        np.save(os.path.join(path, name + ".npy"), np.asarray(val, dtype=np.float64))
 
 
 def algorithmic_flops(n, m, d):
@@ -367,8 +381,13 @@ def main():
     ap.add_argument("--config", choices=sorted(NAMED_CONFIGS), default="c2",
                     help="c2: n=1M m=2048 d=8 (headline, default); c4: n=8M m=4096 d=16 row-sharded (run with --gpus 8); "
                          "c5: the gradient path at the c2 shape, 1 -> 8 GPUs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the C3 / C4-shard block")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the per-stage times, the evidence-only rate, the collective times, the context "
+                         "entry, the other BASELINE configs and the CPU baseline (separate passes after the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the context entry and the C1 / C3 / C4-shard block")
     # validation aids (tests/test_gpu_parity.py runs the N>1 code paths on a 1-GPU box with them); the driver's runs
     # use the defaults: one device per shard, RCCL
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torchrun launch only")
@@ -467,24 +486,27 @@ def main():
     dt = max_over_ranks(time.perf_counter() - t0)
     step_med = max_over_ranks(float(np.median(step_s)))
     assert np.isfinite(ev.l) and np.all(np.isfinite(ev.grad))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ev)
 
-    # ---- separate passes (not part of the headline): per-stage times, evidence only, collective times
-    sp.local.set_timing(2)
-    tim = {}
-    for _ in range(3):
-        step()
-        for k_, v_ in sp.local.last_timings().items():
-            tim.setdefault(k_, []).append(v_)
-    sp.local.set_timing(0)
-    nl_steps = 3
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(nl_steps):
-        ev0 = step(want_grad=False)
-    barrier()
-    dt_nl = max_over_ranks(time.perf_counter() - t1)
-    assert np.isfinite(ev0.l)
-    comm = sp.comm_report(step, tim)
+    # ---- separate passes (--full only, not part of the headline): per-stage times, evidence only, collective times
+    tim, comm = {}, None
+    if args.full:
+        sp.local.set_timing(2)
+        for _ in range(3):
+            step()
+            for k_, v_ in sp.local.last_timings().items():
+                tim.setdefault(k_, []).append(v_)
+        sp.local.set_timing(0)
+        nl_steps = 3
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(nl_steps):
+            ev0 = step(want_grad=False)
+        barrier()
+        dt_nl = max_over_ranks(time.perf_counter() - t1)
+        assert np.isfinite(ev0.l)
+        comm = sp.comm_report(step, tim)
     n_local = sp.n_local
     sp.close()
 
@@ -503,10 +525,6 @@ def main():
         syrk_ms = float(np.mean(kernel_ms)) if kernel_ms else 0.0
         flops_per_launch = float(n_local) * m * m
         achieved = flops_per_launch / (syrk_ms * 1e-3) * 1e-12 if syrk_ms > 0 else None
-        stage = {k_: float(np.mean(v_)) for k_, v_ in sorted(tim.items()) if not k_.startswith("kernel_")}
-        engine_ms = sum(stage.get(k_, 0.0) for k_ in
-                        ("p1_syrk_B", "p2_syrk_W", "p1_trmm_V", "p2_trmm_Q", "p2_trmm_S", "p2_trmm_X", "p2_trmm_SX"))
-        cov_ms = stage.get("p1_cov")
         traffic = profile_traffic(n_local, m) if (n, m, d, n_gpus) == (1_000_000, 2048, 8, 1) else None
         first = traffic["launches"][0] if traffic and traffic["launches"] else None
 
@@ -520,7 +538,7 @@ def main():
             # round 4 the K hyper-parameter sets are drawn BEFORE the timed region (rounds 1-3 drew them between the steps,
             # inside it: ~1 ms per step at this size); the per-step spread is beside it
             "step_ms": {"median": step_med * 1e3, "min": float(np.min(step_s)) * 1e3, "max": float(np.max(step_s)) * 1e3,
-                        "value_at_median": n / step_med},
+                        "value_at_median": n / step_med, "timed_steps": len(step_s)},
             "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "launch": sp.launch if n_gpus > 1 or launched else "single process, one device",
             "config": {"workload": "cov_se_iso FITC nLML + full hyper-gradient, n=%d m=%d d=%d fp64 (%s%s); n row-sharded "
@@ -537,34 +555,38 @@ def main():
                          "avg_launch_ms": syrk_ms, "flops_per_launch": flops_per_launch},
             "roofline_job": {"algorithmic_flops_per_step": F, "achieved": F / (dt / args.steps) * 1e-12 / n_gpus,
                              "peak": PEAK_FP64_MFMA_TFLOPS, "unit": "TFLOP/s per GPU",
-                             "frac": F / (dt / args.steps) * 1e-12 / n_gpus / PEAK_FP64_MFMA_TFLOPS,
-                             "mfma_engine_ms_per_step": engine_ms},
-            # the K_nm builder: HBM-bound while the point dimension is small (d = 8: 2d+~30 flops per 8-byte element),
-            # fp64-VALU/exp-bound from d >= 16 (SURVEY 8(d)); bytes written / its time
-            "roofline_k_builder": {"bound": "hbm" if d < 16 else "valu", "kernel": "gprhip::cov_cross_kernel",
-                                   "achieved": float(n_local) * m * 8 / (cov_ms * 1e-3) * 1e-9 if cov_ms else None,
-                                   "peak": 8000.0, "unit": "GB/s",
-                                   "frac": float(n_local) * m * 8 / (cov_ms * 1e-3) * 1e-9 / 8000.0 if cov_ms else None,
-                                   "algorithmic_bytes_per_step": float(n_local) * m * 8},
-            "stage_ms": stage,
-            "evidence_only": {"value": n * nl_steps / dt_nl, "unit": "training-points/s",
-                              "ms_per_step": dt_nl / nl_steps * 1e3, "steps": nl_steps,
-                              "algorithmic_flops_per_step": F0,
-                              "achieved": F0 / (dt_nl / nl_steps) * 1e-12 / n_gpus, "peak": PEAK_FP64_MFMA_TFLOPS,
-                              "unit_achieved": "TFLOP/s per GPU",
-                              "frac": F0 / (dt_nl / nl_steps) * 1e-12 / n_gpus / PEAK_FP64_MFMA_TFLOPS},
+                             "frac": F / (dt / args.steps) * 1e-12 / n_gpus / PEAK_FP64_MFMA_TFLOPS},
             "last_eval": {"l": float(ev.l), "dl_dsigma2": float(ev.dl_dsigma2),
                           "grad_norm": float(np.linalg.norm(ev.grad))},
         }
+        if args.full:
+            stage = {k_: float(np.mean(v_)) for k_, v_ in sorted(tim.items()) if not k_.startswith("kernel_")}
+            line["roofline_job"]["mfma_engine_ms_per_step"] = sum(stage.get(k_, 0.0) for k_ in (
+                "p1_syrk_B", "p2_syrk_W", "p1_trmm_V", "p2_trmm_Q", "p2_trmm_S", "p2_trmm_X", "p2_trmm_SX"))
+            cov_ms = stage.get("p1_cov")
+            # the K_nm builder: HBM-bound while the point dimension is small (d = 8: 2d+~30 flops per 8-byte element),
+            # fp64-VALU/exp-bound from d >= 16 (SURVEY 8(d)); bytes written / its time
+            line["roofline_k_builder"] = {"bound": "hbm" if d < 16 else "valu", "kernel": "gprhip::cov_cross_kernel",
+                                          "achieved": float(n_local) * m * 8 / (cov_ms * 1e-3) * 1e-9 if cov_ms else None,
+                                          "peak": 8000.0, "unit": "GB/s",
+                                          "frac": float(n_local) * m * 8 / (cov_ms * 1e-3) * 1e-9 / 8000.0 if cov_ms else None,
+                                          "algorithmic_bytes_per_step": float(n_local) * m * 8}
+            line["stage_ms"] = stage
+            line["evidence_only"] = {"value": n * nl_steps / dt_nl, "unit": "training-points/s",
+                                     "ms_per_step": dt_nl / nl_steps * 1e3, "steps": nl_steps,
+                                     "algorithmic_flops_per_step": F0,
+                                     "achieved": F0 / (dt_nl / nl_steps) * 1e-12 / n_gpus, "peak": PEAK_FP64_MFMA_TFLOPS,
+                                     "unit_achieved": "TFLOP/s per GPU",
+                                     "frac": F0 / (dt_nl / nl_steps) * 1e-12 / n_gpus / PEAK_FP64_MFMA_TFLOPS}
         if comm:
             line["multi_gpu"] = comm
         if single_process_multi and args.same_device:
             line["validation_only"] = ("--same-device: the %d shards share device 0, so every per-GPU figure of this line "
                                        "is a sum over shards on one device, not a scaling measurement" % n_gpus)
-        if n_gpus == 1 and not args.no_configs:
+        if args.full and n_gpus == 1 and not args.no_configs:
             line["single_process_context"] = context_entry(gpr_amd, n, m, d, seed)
             line["configs"] = other_configs(gpr_amd)
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(m, d, seed)
         print(json.dumps(line))
     if launched:

@@ -252,15 +252,11 @@ def test_ocaml_stub_file_type_checks_against_the_header():
     assert out.returncode != 0
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/lib/fitc_gp.ml"),
-                    reason="the reference tree exists in the build container only")
 def test_ocaml_smd_step_is_the_references_update():
     """bindings/gpr_hip.ml's Optim.SMD (uncompiled): the pieces of the reference's step that a drop-in must not change
     silently (lib/fitc_gp.ml:1952-1995) are there -- a central difference (gradients at +eps and -eps, scaled by
     lambda / (2 eps)), the nu update with the OLD gains, and the reference's defaults (lambda 0.1, mu 1e-3, eta0 = nu0 =
     1e-3)."""
-    ref = open("/root/reference/lib/fitc_gp.ml").read()
-    assert "scal (lambda /. (2. *. eps)) res" in ref and "Vec.mul old_eta (Vec.add old_gradient lambda_hessian_nu)" in ref
     ml = open(os.path.join(ROOT, "bindings", "gpr_hip.ml")).read()
     smd = ml[ml.index("module SMD = struct"):]
     smd = smd[:smd.index("let test ")]

@@ -623,7 +623,8 @@ def _run_bench(extra, nproc):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--steps", "2", "--warmup", "1", "--points", "20011", "--inducing", "200", "--dims", "4", "--no-cpu-baseline", "--no-configs"]
+    common = ["--steps", "2", "--warmup", "1", "--points", "20011", "--inducing", "200", "--dims", "4", "--full", "--no-cpu-baseline",
+              "--no-configs"]
     if nproc == 1 and not extra:
         cmd = [sys.executable, "bench.py", "--gpus", "1"] + common
     elif "--same-device" in extra or "--expect-failure" in extra:  # ONE process, gprhip_ctx_create(devices[])
@@ -660,6 +661,40 @@ def test_bench_two_ranks_on_one_device_match_single_rank():
     for k in ("l", "dl_dsigma2", "grad_norm"):
         a, b = one["last_eval"][k], two["last_eval"][k]
         assert abs(a - b) <= TOL_BENCH * max(1.0, abs(a)), (k, a, b)
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run (no --full) times the steps and prints the headline fields only; --dump-outputs writes the
+    last timed step's results, which the line's last_eval summarises.  --steps sets the number of timed steps, and the
+    hyper-parameter set of an evaluation depends only on its position: 3 timed steps after 1 warm-up and 2 after 2 end
+    on the same (fourth) set, so the two runs dump the same results bit for bit."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for k, (steps, warmup) in enumerate(((3, 1), (2, 2))):
+        out_dir = tmp_path / ("out%d" % k)
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--points", "20011",
+               "--inducing", "200", "--dims", "4", "--dump-outputs", str(out_dir)]
+        out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        runs.append((json.loads(lines[0]), {f.stem: np.load(f) for f in out_dir.glob("*.npy")}))
+    line, dump = runs[0]
+    assert line["step_ms"]["timed_steps"] == 3 and runs[1][0]["step_ms"]["timed_steps"] == 2
+    assert line["steps"] == 3 and line["ms_per_step"] > 0.0 and line["unit"] == "training-points/s"
+    assert line["dtype"] == "f64" and line["higher_is_better"] is True
+    for k in ("stage_ms", "evidence_only", "configs", "cpu_baseline", "single_process_context", "roofline_k_builder"):
+        assert k not in line, k
+    assert set(dump) == {"l1", "l2", "l", "dl_dsigma2", "grad", "coeffs"}
+    assert all(a.dtype == np.float64 for a in dump.values())
+    assert dump["grad"].shape == (2 + 4 * 200,) and dump["coeffs"].shape == (200,)
+    assert float(dump["l"]) == line["last_eval"]["l"] and float(dump["dl_dsigma2"]) == line["last_eval"]["dl_dsigma2"]
+    assert float(np.linalg.norm(dump["grad"])) == line["last_eval"]["grad_norm"]
+    for k, a in dump.items():
+        assert np.array_equal(a, runs[1][1][k]), k
 
 
 def test_bench_single_process_eight_way_matches_one_gpu_and_torchrun():
@@ -700,7 +735,7 @@ def test_bench_config_c4_launch_on_one_device():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     cmd = [sys.executable, "bench.py", "--gpus", "8", "--config", "c4", "--same-device", "--points", "160003", "--steps", "1",
-           "--warmup", "1", "--no-cpu-baseline", "--no-configs"]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--no-configs"]
     out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])

@@ -4,7 +4,7 @@ root=$(pwd); out=$root/gpurun_out/lab13; mkdir -p $out
 for r in 2048 4096 8192 16384; do
   export GPRHIP_SLICE_ROWS=$r
   echo "SLICE_ROWS=$r"
-  python3 $root/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-configs 2>/dev/null | python3 $root/tools/stage_times.py gt 56 | cut -c1-160
+  python3 $root/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-configs 2>/dev/null | python3 $root/tools/stage_times.py gt 56 | cut -c1-160
   (cd /tmp && export TMPDIR=/tmp && rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $out/f_$r -- python3 $root/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-configs > /dev/null 2>&1)
   db=$(ls $out/f_$r/*/*.db | head -1)
   python3 - "$db" <<'PY'

@@ -5,7 +5,7 @@ root=$(pwd); out=$root/gpurun_out/lab17; mkdir -p $out
 for rep in 1 2; do for v in 1 0; do
   export GPRHIP_NN_DESC=$v
   echo "NN_DESC=$v"
-  python3 $root/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-configs 2>/dev/null | python3 $root/tools/stage_times.py gt 50
+  python3 $root/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-configs 2>/dev/null | python3 $root/tools/stage_times.py gt 50
 done; done
 for v in 1 0; do
   export GPRHIP_NN_DESC=$v

@@ -7,7 +7,7 @@ root=$(pwd); out=$root/gpurun_out/lab19; mkdir -p $out
 for v in 0 1; do
   export GPRHIP_W_AS_WS=$v
   echo "W_AS_WS=$v"
-  python3 $root/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-configs 2>/dev/null | python3 $root/tools/stage_times.py gt 56 | cut -c1-160
+  python3 $root/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-configs 2>/dev/null | python3 $root/tools/stage_times.py gt 56 | cut -c1-160
   (cd /tmp && export TMPDIR=/tmp && rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $out/f_$v -- python3 $root/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-configs > /dev/null 2>&1)
   db=$(ls $out/f_$v/*/*.db | head -1)
   python3 - "$db" <<'PY'

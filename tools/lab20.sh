@@ -3,5 +3,5 @@
 for rep in 1 2; do for v in 0 1; do
   export GPRHIP_W_AS_WS=$v
   echo "W_AS_WS=$v"
-  python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-configs 2>/dev/null | python3 tools/stage_times.py gt 56 | cut -c1-160
+  python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-configs 2>/dev/null | python3 tools/stage_times.py gt 56 | cut -c1-160
 done; done

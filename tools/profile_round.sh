@@ -10,7 +10,7 @@ tag=${1:-rXX}
 root=$(pwd)
 out=$root/gpurun_out
 mkdir -p "$out"
-python3 bench.py --steps 5 --warmup 2 > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"
+python3 bench.py --full --steps 5 --warmup 2 > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d "$out/${tag}_stats" -- python3 "$root/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-configs > "$out/${tag}_stats.log" 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$out/${tag}_pmc_f" -- python3 "$root/bench.py" --steps 1 --warmup 1 --no-cpu-baseline --no-configs > "$out/${tag}_pmc_f.log" 2>&1
