@@ -70,6 +70,19 @@ class Result(C.Structure):
     ]
 
 
+class TargetsResult(C.Structure):
+    """gprhip_targets_result: one evaluation of several target vectors on one model (include/gprhip.h)."""
+    _fields_ = [
+        ("l1", C.c_double),
+        ("l_sum", C.c_double),
+        ("dl_dsigma2_sum", C.c_double),
+        ("n_hypers", C.c_int64),
+        ("k", C.c_int),
+    ]
+
+
+MAX_TARGETS = 16  # GPRHIP_MAX_TARGETS
+
 # name -> (restype, argtypes); the single source of truth for tests/test_abi.py as well
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
@@ -83,10 +96,12 @@ SIGNATURES = {
     "gprhip_problem_destroy": (None, [_vp]),
     "gprhip_set_inputs": (C.c_int, [_vp, _dp, C.c_int64]),
     "gprhip_set_targets": (C.c_int, [_vp, _dp]),
+    "gprhip_set_targets_many": (C.c_int, [_vp, _dp, C.c_int64, C.c_int]),
     "gprhip_set_inputs_device": (C.c_int, [_vp, _vp]),
     "gprhip_set_targets_device": (C.c_int, [_vp, _vp]),
     "gprhip_n_hypers": (C.c_int64, [_vp, C.c_int]),
     "gprhip_eval": (C.c_int, [_vp, C.POINTER(Hypers), C.c_int, C.POINTER(Result), _dp, _dp]),
+    "gprhip_eval_targets": (C.c_int, [_vp, C.POINTER(Hypers), C.c_int, C.POINTER(TargetsResult), _dp, _dp, _dp]),
     "gprhip_ar1_len": (C.c_int64, [_vp]),
     "gprhip_ar2_len": (C.c_int64, [_vp]),
     "gprhip_exchange_len": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -98,6 +113,7 @@ SIGNATURES = {
     "gprhip_stream": (_vp, [_vp]),
     "gprhip_set_timing": (C.c_int, [_vp, C.c_int]),
     "gprhip_predict": (C.c_int, [_vp, _dp, C.c_int64, C.c_int64, C.c_int, _dp, _dp]),
+    "gprhip_predict_targets": (C.c_int, [_vp, _dp, C.c_int64, C.c_int64, _dp]),
     "gprhip_train_stats": (C.c_int, [_vp, _dp, _dp]),
     "gprhip_covariances": (C.c_int, [_vp, _dp, C.c_int64, C.c_int64, C.c_int, C.c_int, _dp]),
     "gprhip_cov_samples": (C.c_int, [_vp, _dp, C.c_int64, C.c_int64, C.c_double, C.c_double, _dp, _dp,

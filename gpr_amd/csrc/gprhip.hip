@@ -241,14 +241,29 @@ struct gprhip_problem {
   int64_t km_rows() const { return d + 2 + (kind == GPRHIP_COV_SE_FAT ? d : 0); }
   // exchange-2 column block: sum E, sum p_k E (d), sum x_big E (D), and for Cov_se_fat sum p_k^2 E (d)
   int64_t col_rows() const { return d + 1 + dbig() + (kind == GPRHIP_COV_SE_FAT ? d : 0); }
+  // several target vectors on one model (gprhip_set_targets_many / gprhip_eval_targets, targets.hip)
+  int tg_k = 0;               // columns of the target matrix held (0: none)
+  int multi = 0;              // the evaluation in flight is one over `multi` target vectors: it takes the engine row path
+  bool multi_state = false;   // the completed evaluation was one: t / w are not those of one target vector
+  double *tg_y = nullptr, *tg_w = nullptr;  // Y and W_mat, column-major [k][nchunks * chunk]
+  double* tg_small = nullptr;  // [y2 (16) | |b_k|^2 (16) | T | T~ | B | c~ (mp x 16 each)]
+  double *tg_part = nullptr, *tg_rowpart = nullptr;  // per-workgroup partials of the tall-skinny products / of the row kernels
+  int64_t tg_bytes = 0;
+  int64_t npad() const { return (int64_t)nchunks * chunk; }
+  double* tg_y2() const { return tg_small; }
+  double* tg_bb() const { return tg_small + TG_LD; }
+  double* tg_T() const { return tg_small + 2 * TG_LD; }
+  double* tg_Tt() const { return tg_T() + (int64_t)mp * TG_LD; }
+  double* tg_B() const { return tg_Tt() + (int64_t)mp * TG_LD; }
+  double* tg_C() const { return tg_B() + (int64_t)mp * TG_LD; }
   bool use_small() const {
-    return small_path && !f32 && !engine_steps && small_path_fits(m, mp, d, has_proj() ? D : 0, n, has_ms());
+    return !multi && small_path && !f32 && !engine_steps && small_path_fits(m, mp, d, has_proj() ? D : 0, n, has_ms());
   }
   // one or two 128-column tiles of inducing points that the small path does not take (65 .. 256 of them, or fewer with more
   // input dimensions than small.hip stages): the row passes and the finish stage of mid.hip
   bool use_mid_gram() const { return mid_gram && n <= MID_GRAM_ROWS; }
   bool use_mid() const {
-    return mid_path && !f32 && !engine_steps && !use_small() && mid_path_fits(m, mp, d, has_proj() ? D : 0, n, has_ms());
+    return !multi && mid_path && !f32 && !engine_steps && !use_small() && mid_path_fits(m, mp, d, has_proj() ? D : 0, n, has_ms());
   }
 };
 
@@ -685,6 +700,44 @@ void cov_chunk(gprhip_problem* p, int c, TS* K, hipStream_t s = nullptr) {
   launch_cov_cross<TS>(p->cp, pts, (int)rows, (int)rows_p, p->Z, p->m, p->mp, p->d, K, s ? s : p->stream, p->zshift);
 }
 
+// ---- several target vectors (targets.hip): the k-column steps around the model-only engine passes
+// Pass 1, after the row vectors: c~ = V^T diag(1/s) Y (m x k) over the resident V, and the k sums y_k^T diag(1/s) y_k
+void targets_pass1(gprhip_problem* p) {
+  hipStream_t s = p->stream;
+  tstart(p, "p1_targets");
+  launch_targets_vty(static_cast<const double*>(p->Vstore), p->mp, p->n, p->mp, 0, p->is, p->tg_y, 1, p->npad(), p->multi,
+                     p->tg_part, p->tg_C(), s);
+  launch_targets_y2(p->tg_y, p->npad(), p->is, p->n, p->multi, p->tg_rowpart, p->tg_y2(), s);
+  tstop(p);
+}
+// Middle: B = R~^-T c~ (column k = Q_n^T y~_k, lib/fitc_gp.ml:285-286), T~ = R~^-1 B, T = U^-1 T~ (:291), |b_k|^2
+void targets_middle(gprhip_problem* p) {
+  hipStream_t s = p->stream;
+  const int mp = p->mp, k = p->multi;
+  tstart(p, "mid_targets");
+  launch_targets_vty(p->rinv, mp, mp, mp, 1, nullptr, p->tg_C(), TG_LD, 1, k, p->tg_part, p->tg_B(), s);
+  launch_targets_colsq(p->tg_B(), mp, p->tg_bb(), s);
+  launch_targets_rows(p->rinv, mp, mp, mp, 1, p->tg_B(), k, p->tg_Tt(), TG_LD, 1, s);
+  launch_targets_rows(p->uinv, mp, mp, mp, 1, p->tg_Tt(), k, p->tg_T(), TG_LD, 1, s);
+  tstop(p);
+}
+// Pass 2, one row chunk, after the Q' launch and the (model-only) row kernel: W_mat = diag(1/s) (Y - Q' B), then
+// v = v1 - mean_k w_k^2 and the row sums of E accordingly
+void targets_pass2_rows(gprhip_problem* p, const double* Q, int64_t base, int rows, double* es, double* sumv) {
+  hipStream_t s = p->stream;
+  tstart(p, "p2_targets");
+  launch_targets_rows(Q, p->mp, rows, p->mp, 0, p->tg_B(), p->multi, p->tg_w + base, 1, p->npad(), s);
+  launch_targets_p2_rows(p->tg_y + base, p->tg_w + base, p->npad(), p->is + base, p->r + base, p->cp.sf2, rows, p->multi,
+                         p->v + base, es, p->tg_rowpart, sumv, s);
+  tstop(p);
+}
+// ... after the X launch (run with w = 0): X -= (1/k) W_mat T^T, the rank-k form of the ger of lib/fitc_gp.ml:1204-1206
+void targets_xcorr(gprhip_problem* p, double* X, int64_t base, int rows) {
+  tstart(p, "p2_xcorr");
+  launch_targets_xcorr(X, rows, p->mp, p->tg_w + base, p->npad(), p->tg_T(), p->multi, p->stream);
+  tstop(p);
+}
+
 template <typename TS>
 void do_pass1(gprhip_problem* p, const gprhip_hypers* h, int want_grad, int64_t n_total, double* ar1) {
   if (!h || !h->inducing) {
@@ -699,6 +752,7 @@ void do_pass1(gprhip_problem* p, const gprhip_hypers* h, int want_grad, int64_t 
   hipStream_t s = p->stream;
   // the state of the previous evaluation is void from here on; finish() re-validates it
   p->have_model = p->have_factors = false;
+  p->multi_state = false;
   p->stage = 0;
   p->x_last = nullptr;
   p->cond_km = -1.0;
@@ -985,6 +1039,8 @@ void do_pass2(gprhip_problem* p, const double* ar1, double* ar2) {
     launch_triu_matvec(p->uinv, mp, p->ttil, p->tvec, 0, s);
   }
   tstop(p);
+  if constexpr (std::is_same<TS, double>::value)
+    if (p->multi) targets_middle(p);  // (c~, b, t~, t above are those of no target: zero)
 
   // evidence-only evaluations (multim_f) carry nothing in the second exchange buffer: only its scalar tail is cleared,
   // and the caller need not reduce it
@@ -1130,6 +1186,8 @@ void do_pass2(gprhip_problem* p, const double* ar1, double* ar2) {
       launch_pass2_rows(ra, s);
       launch_reduce_rows(p->rowpart, pass1_row_blocks(rows_p), 4, ar2_tail, 1, s);
       tstop(p);
+      if constexpr (std::is_same<TS, double>::value)
+        if (p->multi) targets_pass2_rows(p, bufA, base, (int)rows, proj ? p->es + base : nullptr, ar2_tail + A2_SUMV);
       const TS* Xc;  // X of this chunk
       if (p->merged_x) {
         // X = diag(is) Q' R^-T - diag(v) V U^-T - w t^T  (S, U_mat and the ger of lib/fitc_gp.ml:931-939, :1204-1206) as
@@ -1163,6 +1221,8 @@ void do_pass2(gprhip_problem* p, const double* ar1, double* ar2) {
         Xc = bufA;
       }
       p->x_last = (p->nchunks == 1) ? static_cast<const void*>(Xc) : nullptr;
+      if constexpr (std::is_same<TS, double>::value)
+        if (p->multi) targets_xcorr(p, const_cast<double*>(Xc), base, (int)rows);
       tstart(p, "p2_grad");
       GradArgs<TS> ga;
       ga.X = Xc; ga.pts = p->pts() + base * p->d; ga.Z = p->Z;
@@ -1313,6 +1373,7 @@ void do_finish_enqueue(gprhip_problem* p, const double* ar2, bool light = false)
   if (p->want_grad) {
     tstart(p, "finish");
     launch_build_w(p->binv, p->ttil, ar2, mp, p->wtil, s);
+    if (p->multi) launch_targets_w_rankk(p->wtil, mp, p->tg_Tt(), p->multi, s);  // (1/k) T~ T~^T in place of t~ t~^T (zero here)
     GemmArgs y;  // Y = W~ U^-T
     y.A = p->wtil; y.lda = mp; y.B = p->uinv; y.ldb = mp; y.C = p->kj; y.ldc = mp;  // kj is free after potrf; R~ stays in bmat
     y.M = mp; y.N = mp; y.K = mp; y.tri = TRI_KLO_BN;
@@ -1494,6 +1555,11 @@ void do_predict(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_
   }
   if (variances && !p->have_factors) {
     set_error("gprhip_predict: the loaded predictor has no co-variance coefficients (chol_km, r_mat)");
+    throw HipFail{ST_STATE};
+  }
+  if (means && p->multi_state) {
+    set_error("gprhip_predict: the last evaluation was gprhip_eval_targets (several target vectors): means come from "
+              "gprhip_predict_targets, or from gprhip_predict after the next gprhip_eval");
     throw HipFail{ST_STATE};
   }
   if (means) need_trustworthy_coeffs(p, "gprhip_predict");
@@ -1724,6 +1790,11 @@ void need_model(gprhip_problem* p, const char* who) {
 template <typename TS>
 void do_train_stats(gprhip_problem* p, double* means, double* sums) {
   need_model(p, "gprhip_train_stats");
+  if (p->multi_state) {
+    set_error("gprhip_train_stats: the last evaluation was gprhip_eval_targets (several target vectors); the statistics are "
+              "those of one target vector and need a gprhip_eval");
+    throw HipFail{ST_STATE};
+  }
   if (!p->have_targets || p->h.model_only) {
     set_error("gprhip_train_stats: the last evaluation had no targets");
     throw HipFail{ST_STATE};
@@ -1919,6 +1990,7 @@ void do_load_predictor(gprhip_problem* p, const gprhip_hypers* h, const double* 
   const int mp = p->mp, m = p->m;
   const int64_t mm = (int64_t)mp * mp;
   p->have_model = p->have_factors = p->have_v = p->have_k = false;
+  p->multi_state = false;
   p->cond_km = -1.0;
   upload_hypers(p, h);
   std::vector<double> t(mp, 0.0);
@@ -1950,6 +2022,156 @@ void do_load_predictor(gprhip_problem* p, const gprhip_hypers* h, const double* 
   p->stage = 0;
   p->have_model = true;
   p->h.model_only = coeffs ? 0 : 1;
+}
+
+// gprhip_set_targets_many: the n x k device buffers (and the m x k ones) are made here, not inside an evaluation
+void do_set_targets_many(gprhip_problem* p, const double* targets, int64_t ld, int k) {
+  GPR_HIP(hipSetDevice(p->device));
+  const int mp = p->mp;
+  const int64_t npad = p->npad();
+  if (p->tg_k != k) {
+    const int64_t n_small = 2 * TG_LD + 4 * (int64_t)mp * TG_LD;
+    const int64_t n_part = (int64_t)std::max(targets_vty_blocks(p->n), targets_vty_blocks(mp)) * mp * TG_LD;
+    const int64_t n_rowpart = ((npad + 255) / 256) * TG_LD;
+    const int64_t need = (2 * (int64_t)k * npad + n_small + n_part + n_rowpart) * 8;
+    GPR_HIP(hipStreamSynchronize(p->stream));
+    size_t free_b = 0, total_b = 0;
+    GPR_HIP(hipMemGetInfo(&free_b, &total_b));
+    // (what an earlier target matrix holds comes back first; the V store of a problem not yet evaluated is still to come)
+    const int64_t v_store = p->Vstore ? 0 : npad * mp * (int64_t)p->esz;
+    if ((uint64_t)(need + v_store) > (uint64_t)free_b + (uint64_t)p->tg_bytes) {
+      char buf[256];
+      snprintf(buf, sizeof buf, "gprhip_set_targets_many: %d target vectors need %.3f GB on device %d (%.3f GB of it the V store "
+               "the first evaluation adds) and %.3f GB are free", k, (need + v_store) / 1e9, p->device, v_store / 1e9,
+               (free_b + p->tg_bytes) / 1e9);
+      set_error(buf);
+      throw HipFail{ST_OOM};
+    }
+    auto release = [p](double*& q) {
+      if (!q) return;
+      auto it = std::find(p->allocs.begin(), p->allocs.end(), static_cast<void*>(q));
+      if (it != p->allocs.end()) p->allocs.erase(it);
+      (void)hipFree(q);
+      q = nullptr;
+    };
+    release(p->tg_y); release(p->tg_w); release(p->tg_small); release(p->tg_part); release(p->tg_rowpart);
+    p->alloc_bytes -= p->tg_bytes;
+    p->tg_k = 0;
+    p->tg_bytes = 0;
+    const int64_t before = p->alloc_bytes;
+    try {
+      p->tg_y = p->alloc<double>((int64_t)k * npad);
+      p->tg_w = p->alloc<double>((int64_t)k * npad);
+      p->tg_small = p->alloc<double>(n_small);
+      p->tg_part = p->alloc<double>(n_part);
+      p->tg_rowpart = p->alloc<double>(n_rowpart);
+    } catch (...) {
+      // (the pre-check passed and an allocation failed all the same: nothing half-made stays -- the problem holds no target
+      //  matrix, and its byte count is what it was without one)
+      release(p->tg_y); release(p->tg_w); release(p->tg_small); release(p->tg_part); release(p->tg_rowpart);
+      p->alloc_bytes = before;
+      throw;
+    }
+    p->tg_bytes = p->alloc_bytes - before;
+    GPR_HIP(hipMemsetAsync(p->tg_y, 0, (size_t)k * npad * sizeof(double), p->stream));
+    GPR_HIP(hipMemsetAsync(p->tg_w, 0, (size_t)k * npad * sizeof(double), p->stream));
+    GPR_HIP(hipMemsetAsync(p->tg_small, 0, (size_t)n_small * sizeof(double), p->stream));
+  }
+  GPR_HIP(hipMemcpy2DAsync(p->tg_y, (size_t)npad * sizeof(double), targets, (size_t)ld * sizeof(double),
+                           (size_t)p->n * sizeof(double), (size_t)k, hipMemcpyHostToDevice, p->stream));
+  GPR_HIP(hipStreamSynchronize(p->stream));
+  p->tg_k = k;
+}
+
+// gprhip_eval_targets: the model parts of the evaluation run once as a model-only evaluation on the engine row path (v1, the
+// model terms of W and X); the k-column steps of targets.hip put mean_k of the target terms in (v, W~, X are linear in them),
+// and the assembled gradient of the mean is multiplied by k.
+void do_eval_targets(gprhip_problem* p, const gprhip_hypers* h, int want_grad, gprhip_targets_result* res, double* l2,
+                     double* grad_sum, double* coeffs) {
+  const int k = p->tg_k;
+  gprhip_hypers hm = *h;
+  hm.model_only = 1;
+  gprhip_result r{};
+  p->multi = k;
+  try {
+    do_pass1<double>(p, &hm, want_grad, p->n, p->ar1);
+    targets_pass1(p);
+    do_pass2<double>(p, p->ar1, p->ar2);
+    do_finish_enqueue(p, p->ar2);
+    do_finish_collect(p, &r, grad_sum, nullptr);
+  } catch (...) {
+    p->multi = 0;
+    throw;
+  }
+  p->multi = 0;
+  p->multi_state = true;
+  const int m = p->m;
+  std::vector<double> hs(2 * TG_LD + (size_t)p->mp * TG_LD);
+  GPR_HIP(hipMemcpy(hs.data(), p->tg_small, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
+  res->l1 = r.l1;
+  res->k = k;
+  res->n_hypers = r.n_hypers;
+  double l2sum = 0.0;
+  for (int kk = 0; kk < k; ++kk) {
+    l2[kk] = -0.5 * (hs[kk] - hs[TG_LD + kk]);  // -1/2 (|y~_k|^2 - |Q_n^T y~_k|^2), lib/fitc_gp.ml:290
+    l2sum += l2[kk];
+  }
+  res->l_sum = k * r.l1 + l2sum;
+  res->dl_dsigma2_sum = k * r.dl_dsigma2;
+  if (want_grad)
+    for (int64_t i = 0; i < r.n_hypers; ++i) grad_sum[i] *= k;
+  if (coeffs) {
+    const double* T = hs.data() + 2 * TG_LD;
+    for (int kk = 0; kk < k; ++kk)
+      for (int i = 0; i < m; ++i) coeffs[(size_t)kk * m + i] = T[(size_t)i * TG_LD + kk];
+  }
+}
+
+// Means.calc (lib/fitc_gp.ml:418-425) per target column: means = K_tm T, test points in chunks of the training chunk
+void do_predict_targets(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_t nt, double* means) {
+  need_model(p, "gprhip_predict_targets");
+  if (!p->multi_state || !p->tg_k) {
+    set_error("gprhip_predict_targets: the last evaluation on this problem was not a gprhip_eval_targets");
+    throw HipFail{ST_STATE};
+  }
+  GPR_HIP(hipSetDevice(p->device));
+  hipStream_t s = p->stream;
+  const int mp = p->mp, k = p->tg_k;
+  const int64_t chunk = p->chunk, npad = p->npad();
+  if (!p->xt || p->xt_rows < chunk) {
+    GPR_HIP(hipStreamSynchronize(s));
+    auto release = [p](double*& q) {
+      if (!q) return;
+      auto it = std::find(p->allocs.begin(), p->allocs.end(), static_cast<void*>(q));
+      if (it != p->allocs.end()) p->allocs.erase(it);
+      (void)hipFree(q);
+      q = nullptr;
+    };
+    release(p->xt); release(p->pt); release(p->prow);
+    p->xt_rows = 0;
+    p->xt = p->alloc<double>(chunk * p->D);
+    p->pt = p->alloc<double>(chunk * p->d);
+    p->prow = p->alloc<double>(3 * chunk);
+    p->xt_rows = chunk;
+  }
+  double* const K = static_cast<double*>(p->bufA);
+  for (int64_t lo = 0; lo < nt; lo += chunk) {
+    const int rows = (int)std::min<int64_t>(chunk, nt - lo);
+    const int rows_p = (int)round_up(rows, TILE);
+    GPR_HIP(hipMemcpy2DAsync(p->xt, (size_t)p->D * sizeof(double), test_inputs + lo * ld, (size_t)ld * sizeof(double),
+                             (size_t)p->D * sizeof(double), (size_t)rows, hipMemcpyHostToDevice, s));
+    const double* pts = p->xt;
+    if (p->has_proj()) {
+      launch_project(p->xt, rows, p->D, p->d, p->tproj, p->pt, s);
+      pts = p->pt;
+    }
+    launch_cov_cross<double>(p->cp, pts, rows, rows_p, p->Z, p->m, mp, p->d, K, s);
+    launch_targets_rows(K, mp, rows, mp, 0, p->tg_T(), k, p->tg_w, 1, npad, s);  // (W_mat is scratch between evaluations)
+    GPR_HIP(hipMemcpy2DAsync(means + lo, (size_t)nt * sizeof(double), p->tg_w, (size_t)npad * sizeof(double),
+                             (size_t)rows * sizeof(double), (size_t)k, hipMemcpyDeviceToHost, s));
+    GPR_HIP(hipStreamSynchronize(s));
+  }
+  p->x_last = nullptr;  // (the chunk buffer that may have held X has been overwritten)
 }
 
 void tdrop(gprhip_problem* p) {  // a failed evaluation leaves its stage timers behind
@@ -2378,6 +2600,53 @@ int gprhip_eval(gprhip_problem* p, const gprhip_hypers* h, int want_grad, gprhip
     do_finish_enqueue(p, p->ar2);
     do_finish_collect(p, res, grad, coeffs);
   }, p);
+}
+
+int gprhip_set_targets_many(gprhip_problem* p, const double* targets, int64_t ld, int k) {
+  return guarded([&] {
+    if (!p || !targets || k < 1 || k > GPRHIP_MAX_TARGETS || ld < p->n) {
+      set_error("gprhip_set_targets_many: invalid arguments (need 1 <= k <= GPRHIP_MAX_TARGETS, ld >= n)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (p->f32) {
+      set_error("gprhip_set_targets_many: several target vectors are evaluated in fp64 only (GPRHIP_F32_BULK problem)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    do_set_targets_many(p, targets, ld, k);
+  }, p);
+}
+
+int gprhip_eval_targets(gprhip_problem* p, const gprhip_hypers* h, int want_grad, gprhip_targets_result* res, double* l2,
+                        double* grad_sum, double* coeffs) {
+  return guarded([&] {
+    if (!p || !h || !res || !l2 || (want_grad && !grad_sum)) {
+      set_error("gprhip_eval_targets: NULL argument");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (p->f32) {
+      set_error("gprhip_eval_targets: several target vectors are evaluated in fp64 only (GPRHIP_F32_BULK problem)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (h->model_only) {
+      set_error("gprhip_eval_targets: model_only = 1 (an evaluation without targets is gprhip_eval)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (!p->tg_k) {
+      set_error("gprhip_eval_targets: no target matrix set (gprhip_set_targets_many)");
+      throw HipFail{ST_STATE};
+    }
+    do_eval_targets(p, h, want_grad, res, l2, grad_sum, coeffs);
+  }, p);
+}
+
+int gprhip_predict_targets(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_t nt, double* means) {
+  return guarded([&] {
+    if (!p || !test_inputs || !means || nt < 1 || ld < p->D) {
+      set_error("gprhip_predict_targets: invalid arguments");
+      throw HipFail{ST_BAD_ARG};
+    }
+    do_predict_targets(p, test_inputs, ld, nt, means);
+  });
 }
 
 int gprhip_predict(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_t nt, int predictive,

@@ -365,4 +365,30 @@ int64_t mid_gram_part_len();
 void launch_mid_gram(const MidGramArgs& a, double* tiles, double* cvec, hipStream_t s);
 void launch_mid_transposes(const double* uinv, const double* rinv, int mp, double* uinvT, double* rinvT, hipStream_t s);
 
+// ---- several target vectors on one model (targets.hip): the k-column forms of the single-vector steps of the engine row
+// path.  Small m x k matrices are row-major [mp][TG_LD] with columns >= k zero; n x k matrices are column-major [k][ld].
+constexpr int TG_LD = 16;  // GPRHIP_MAX_TARGETS
+int targets_vty_blocks(int64_t rows);  // row blocks (= partial slabs of mp * TG_LD doubles) of launch_targets_vty over `rows` rows
+// out [mp][TG_LD] = A^T diag(w) Y over the rows of A [rows][lda >= mp] (w null: weights 1); Y element (r, kk) at
+// Y[r * y_rs + kk * y_cs]; upper: A is an upper-triangular mp x mp factor.  part: targets_vty_blocks(rows) slabs.
+void launch_targets_vty(const double* A, int64_t lda, int64_t rows, int mp, int upper, const double* w, const double* Y,
+                        int64_t y_rs, int64_t y_cs, int k, double* part, double* out, hipStream_t s);
+// out element (r, kk) at out[r * o_rs + kk * o_cs] = sum_j A[r][j] Bm[j][kk], r < rows, kk < k
+void launch_targets_rows(const double* A, int64_t lda, int64_t rows, int mp, int upper, const double* Bm, int k,
+                         double* out, int64_t o_rs, int64_t o_cs, hipStream_t s);
+// out[TG_LD] = sum_r is[r] Y[kk][r]^2; part: ceil(rows / 256) * TG_LD doubles
+void launch_targets_y2(const double* Y, int64_t ld, const double* is, int64_t rows, int k, double* part, double* out,
+                       hipStream_t s);
+// out[TG_LD] = column sums of Bm.^2
+void launch_targets_colsq(const double* Bm, int mp, double* out, hipStream_t s);
+// rows of one chunk after the model-only row pass: Wm (in: Q' b_k, out: w_k), v -= mean_k w_k^2, and es (may be null) from
+// q - v1 (sf2 - r) to q - v (sf2 - r) - mean_k w_k (Q' b_k) with the new v; *sumv += the sum of the change of v.
+// part: ceil(rows / 256) doubles
+void launch_targets_p2_rows(const double* Y, double* Wm, int64_t ld, const double* is, const double* r, double sf2, int rows,
+                            int k, double* v, double* es, double* part, double* sumv, hipStream_t s);
+// X [rows][mp] -= (1/k) Wm T^T
+void launch_targets_xcorr(double* X, int rows, int mp, const double* Wm, int64_t ld, const double* T, int k, hipStream_t s);
+// W~ [mp][mp] (full) -= (1/k) Tt Tt^T
+void launch_targets_w_rankk(double* W, int mp, const double* Tt, int k, hipStream_t s);
+
 }  // namespace gprhip

@@ -106,6 +106,51 @@ class _Trained:
             self._ev = _run(self.model, self.targets, self.want_grad, self)
 
 
+class _TrainedMany:
+    """Several target vectors (the columns of an n x k matrix) on one model, evaluated in ONE device evaluation
+    (`Problem.eval_targets`) -- an extension beyond the reference's signature, whose Trained.t holds one target vector.
+    Owns the device state like _Trained does; the state it leaves is the model's (chol_km, r_mat) and the k columns of
+    mean coefficients, not the single-target state."""
+
+    def __init__(self, model, targets, want_grad):
+        self.model = model
+        self.targets = np.asfortranarray(targets, dtype=np.float64)
+        n = model.inputs.problem.n
+        if self.targets.ndim != 2 or self.targets.shape[0] != n:
+            raise ValueError("Trained.calc_many: expected targets of shape (%d, k), got %s" % (n, self.targets.shape))
+        self.want_grad = want_grad
+        self._ev = None
+
+    def evaluation(self):
+        if self._ev is None:
+            self._ev = _run_many(self)
+        return self._ev
+
+    def ensure_state(self):
+        if self._ev is None or getattr(self.model.inputs.problem, "_state_owner", None) is not self:
+            self._ev = _run_many(self)
+
+
+def _run_many(trained):
+    """As _run, through Problem.eval_targets (same reuse_v signature, same ownership of the device state)."""
+    model = trained.model
+    inputs = model.inputs
+    prob = inputs.problem
+    kernel = inputs.inducing.kernel
+    if getattr(prob, "_targets_many_ref", None) is not trained.targets:
+        prob.set_targets_many(trained.targets)
+        prob._targets_many_ref = trained.targets
+    sig = (id(kernel), id(inputs.inducing.points))
+    reuse = getattr(prob, "_last_sig", None) == sig
+    prob._last_sig = prob._state_owner = None
+    ev = prob.eval_targets(sigma2=model.sigma2, inducing=inputs.inducing.points, variational=model.variational,
+                           want_grad=trained.want_grad, jitter=prob._jitter, reuse_v=reuse, **prob._spec.eval_args(kernel))
+    prob._last_sig = sig
+    prob._state_owner = trained
+    prob._last_refs = (kernel, inputs.inducing.points)
+    return ev
+
+
 class _HyperT:
     def __init__(self, evaluation, kernel, inducing_points, spec):
         self.evaluation, self.kernel, self.inducing_points, self.spec = evaluation, kernel, inducing_points, spec
@@ -263,6 +308,30 @@ def _make_variant(spec, variational, functor, cov_kind="FITC"):
             calc_mean_coeffs=lambda trained: trained.evaluation().coeffs,  # :294
             get_model=lambda trained: trained.model, get_targets=lambda trained: trained.targets),
     )
+
+    def _log_evidence(trained):  # :295; for a Trained.calc_many object: the sum over its target vectors
+        ev = trained.evaluation()
+        return ev.l_sum if isinstance(trained, _TrainedMany) else ev.l
+
+    def _many(trained):
+        if not isinstance(trained, _TrainedMany):
+            raise TypeError("expected the object of Trained.calc_many")
+        return trained.evaluation()
+
+    Eval.Trained.calc_log_evidence = _log_evidence
+    Eval.Trained.calc_many = lambda model, targets: _TrainedMany(model, targets, False)
+    Eval.Trained.calc_log_evidences = lambda trained: _many(trained).l.copy()   # k values
+    # (calc_mean_coeffs needs no change: both kinds of object carry `coeffs`, m entries or m x k)
+
+    def predict_many(trained, inputs):
+        """Means.calc for every target column of a Trained.calc_many object: nt x k."""
+        if inputs.inducing.points is not trained.model.inputs.inducing.points:
+            raise ValueError("Means.calc: trained and inputs disagree about inducing points")
+        _many(trained)
+        trained.ensure_state()
+        return trained.model.inputs.problem.predict_targets(inputs.points)
+
+    Eval.Trained.calc_means_many = predict_many
 
     # ---- prediction (lib/fitc_gp.ml:377-531): means and variances at new inputs, on the device that
     # holds the trained model's state
@@ -502,8 +571,15 @@ def _make_variant(spec, variational, functor, cov_kind="FITC"):
                     "differ by more than %f on %s" % (finite_el, deriv, tol, name))
 
     def calc_gradient(learn_sigma2, sigma2, hypers, trained):
-        """Optim.calc_gradient (lib/fitc_gp.ml:1674-1694)."""
+        """Optim.calc_gradient (lib/fitc_gp.ml:1674-1694).  A `Trained.calc_many` object gives the gradient of the summed
+        log evidence of its target vectors."""
         ev = trained.evaluation()
+        if isinstance(trained, _TrainedMany):
+            inducing = trained.model.inputs.inducing
+            g = [float(ev.grad_sum[spec.HyperModule.index_of(inducing.kernel, inducing.points, h)]) for h in hypers]
+            if learn_sigma2:
+                g = [ev.dl_dsigma2_sum * sigma2] + g
+            return np.array(g)
         ht = prepare_hyper_trained(trained)
         g = [hyper_lookup(ht, h) for h in hypers]
         if learn_sigma2:
@@ -522,7 +598,10 @@ def _make_variant(spec, variational, functor, cov_kind="FITC"):
             calc=lambda model, targets: _Trained(model, targets, True),                 # :1158-1181
             calc_eval=lambda t: t,
             calc_log_evidence_sigma2=lambda trained: trained.evaluation().dl_dsigma2,   # :1187-1188
-            prepare_hyper=prepare_hyper_trained, calc_log_evidence=hyper_lookup),
+            prepare_hyper=prepare_hyper_trained, calc_log_evidence=hyper_lookup,
+            # extension beyond the reference's signature: k target vectors (n x k) on one model in one evaluation.  The
+            # object answers the three *_many functions of Eval.Trained below and Deriv.Optim.calc_gradient
+            calc_many=lambda model, targets: _TrainedMany(model, targets, True)),
         Test=SimpleNamespace(self_test=self_test),
         Optim=SimpleNamespace(calc_gradient=calc_gradient),
     )

@@ -16,6 +16,7 @@ from ._lib import NotPositiveDefinite
 def train(functor_variant, spec, kernel, inducing, inputs, targets, sigma2=None, learn_sigma2=True,
           hypers=None, max_iter=100, tol=1e-6, report=None):
     """Returns (kernel, inducing, sigma2, log_evidence, n_evaluations) at the best point found.
+    targets: n, or n x k for k GPs with shared hyper-parameters (log_evidence is then the sum over the columns).
 
     functor_variant: e.g. fitc_gp.Make_deriv(cov_se_iso).FITC ; hypers: subset to optimise
     (the reference's ?hypers, lib/fitc_gp.ml:1535), default Hyper.get_all."""
@@ -23,7 +24,13 @@ def train(functor_variant, spec, kernel, inducing, inputs, targets, sigma2=None,
 
     F = functor_variant
     H = spec.HyperModule
-    targets = np.ascontiguousarray(targets, dtype=np.float64)
+    many = np.ndim(targets) == 2  # n x k: one GP per column with shared hyper-parameters, the summed evidence maximised
+    if many:
+        targets = np.asfortranarray(targets, dtype=np.float64)
+        if sigma2 is None:  # Optim.get_sigma2 per column, averaged
+            sigma2 = float(np.mean(np.sum(targets * targets, axis=0))) / targets.shape[0]
+    else:
+        targets = np.ascontiguousarray(targets, dtype=np.float64)
     if sigma2 is None:  # Optim.get_sigma2, lib/fitc_gp.ml:1468-1469
         sigma2 = float(targets @ targets) / targets.shape[0]
     if hypers is None:
@@ -44,7 +51,7 @@ def train(functor_variant, spec, kernel, inducing, inputs, targets, sigma2=None,
             k, z, s2 = unpack(x)
             ind = F.Deriv.Inducing.calc(k, z)
             model = F.Deriv.Model.calc(F.Deriv.Inputs.calc(ind, inputs), sigma2=s2)
-            trained = F.Deriv.Trained.calc(model, targets=targets)
+            trained = (F.Deriv.Trained.calc_many if many else F.Deriv.Trained.calc)(model, targets)
             le = F.Eval.Trained.calc_log_evidence(trained)
             g = F.Deriv.Optim.calc_gradient(learn_sigma2, s2, hypers, trained)
             ok = np.isfinite(le) and np.all(np.isfinite(g))

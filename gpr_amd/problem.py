@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import COV_SE_FAT, COV_SE_ISO, F32_BULK, F64, Hypers, Result
+from ._lib import COV_SE_FAT, COV_SE_ISO, F32_BULK, F64, Hypers, Result, TargetsResult
 
 CHOLESKY_JITTER = 1e-6  # Utils.cholesky_jitter, lib/utils.ml:35
 
@@ -26,6 +26,18 @@ class Evaluation:
     dl_dsigma2: Optional[float]
     grad: Optional[np.ndarray]    # reference Hyper.get_all order
     coeffs: np.ndarray        # Trained.calc_mean_coeffs
+
+
+@dataclass
+class TargetsEvaluation:
+    """One evaluation of k target vectors on one model (Problem.eval_targets)."""
+    l1: float                 # Model.calc_log_evidence (the same for every target)
+    l2: np.ndarray            # [k]
+    l: np.ndarray             # [k] Trained.calc_log_evidence per target
+    l_sum: float              # sum of l
+    dl_dsigma2_sum: Optional[float]
+    grad_sum: Optional[np.ndarray]  # gradient of l_sum, reference Hyper.get_all order
+    coeffs: np.ndarray        # m x k, column j = Trained.calc_mean_coeffs of target j
 
 
 def _f64_ptr(a):
@@ -75,6 +87,15 @@ class Problem:
             # Trained.calc: Vec.dim targets <> n  (lib/fitc_gp.ml:283-284)
             raise ValueError("Trained.calc: Vec.dim targets (%d) <> n (%d)" % (y.shape[0], self.n))
         _lib.check(self._lib.gprhip_set_targets(self._handle(), _f64_ptr(y)))
+
+    def set_targets_many(self, targets):
+        """targets: n x k (one target vector per column), 1 <= k <= 16; replaces any earlier target matrix.  The target
+        vector of `set_targets` is kept beside it."""
+        y = np.asfortranarray(targets, dtype=np.float64)
+        if y.ndim != 2 or y.shape[0] != self.n:
+            raise ValueError("Trained.calc_many: expected targets of shape (%d, k), got %s" % (self.n, y.shape))
+        _lib.check(self._lib.gprhip_set_targets_many(self._handle(), _f64_ptr(y), self.n, int(y.shape[1])))
+        self._k = int(y.shape[1])
 
     def set_inputs_device(self, ptr):
         """ptr: device address of a contiguous point-major [n][D] fp64 array (e.g. tensor.data_ptr())."""
@@ -135,6 +156,38 @@ class Problem:
         del keep
         return Evaluation(res.l1, res.l2, res.l, res.dl_dsigma2 if want_grad else None,
                           grad[:res.n_hypers] if want_grad else None, coeffs)
+
+    def eval_targets(self, *, log_sf2, sigma2, inducing, log_ell=0.0, tproj=None, variational=False,
+                     model_only=False, want_grad=True, jitter=CHOLESKY_JITTER, log_hetero_skedasticity=None,
+                     log_multiscales_m05=None, reuse_v=False):
+        """All target vectors of `set_targets_many` against one model in one evaluation: per-target evidence and mean
+        coefficients, the gradient of the summed log evidence.  Keyword arguments as `eval` (model_only is refused)."""
+        h, keep = self._hypers(log_ell, log_sf2, sigma2, inducing, tproj, variational, model_only, jitter,
+                               log_hetero_skedasticity, log_multiscales_m05, reuse_v)
+        res = TargetsResult()
+        nh = self.n_hypers(tproj is not None, log_hetero_skedasticity is not None, log_multiscales_m05 is not None)
+        grad = np.empty(nh if want_grad else 1, dtype=np.float64)
+        l2 = np.zeros(_lib.MAX_TARGETS, dtype=np.float64)
+        coeffs = np.zeros((self.m, _lib.MAX_TARGETS), dtype=np.float64, order="F")
+        _lib.check(self._lib.gprhip_eval_targets(self._handle(), C.byref(h), int(want_grad), C.byref(res), _f64_ptr(l2),
+                                                 _f64_ptr(grad), _f64_ptr(coeffs)))
+        del keep
+        k = int(res.k)
+        l2 = l2[:k].copy()
+        return TargetsEvaluation(res.l1, l2, res.l1 + l2, res.l_sum, res.dl_dsigma2_sum if want_grad else None,
+                                 grad[:res.n_hypers] if want_grad else None, np.asfortranarray(coeffs[:, :k]))
+
+    def predict_targets(self, test_inputs):
+        """Means.calc per target column (lib/fitc_gp.ml:418-425) at test points (D x nt) with the coefficients of the last
+        `eval_targets`: nt x k."""
+        xt = np.asfortranarray(test_inputs, dtype=np.float64)
+        if xt.ndim != 2 or xt.shape[0] != self.D:
+            raise ValueError("predict_targets: expected test inputs of shape (%d, nt)" % self.D)
+        nt = xt.shape[1]
+        k = getattr(self, "_k", 0)
+        means = np.empty((nt, max(k, 1)), dtype=np.float64, order="F")
+        _lib.check(self._lib.gprhip_predict_targets(self._handle(), _f64_ptr(xt), self.D, nt, _f64_ptr(means)))
+        return means
 
     # ---- prediction (SURVEY 8(f) rank 1)
     def predict(self, test_inputs, predictive=True, want_variances=True):

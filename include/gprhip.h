@@ -97,6 +97,44 @@ int gprhip_set_targets(gprhip_problem* p, const double* targets);
 int gprhip_set_inputs_device(gprhip_problem* p, const double* d_inputs);
 int gprhip_set_targets_device(gprhip_problem* p, const double* d_targets);
 
+/* ---- Several target vectors on one model ---------------------------------------------------------------------------
+ * The reference separates Model (kernel, inducing points, inputs, sigma2) from Trained (a model plus ONE target vector) so
+ * that one model serves many target vectors: everything expensive depends on the model only, a target vector adds
+ * O(n m) work (lib/fitc_gp.ml:279-292, :1158-1207).  These three calls evaluate up to GPRHIP_MAX_TARGETS target vectors
+ * against one model in ONE evaluation -- multi-output regression with shared hyper-parameters: one GP per column, the
+ * log evidence summed.  The gradient entries are linear in (v, W, X) (lib/fitc_gp.ml:1005-1021), so the model parts run
+ * once and the two rank-1 target terms become rank-k terms.
+ *
+ *   gprhip_set_targets_many   Fortran n x k host matrix (ld >= n), 1 <= k <= GPRHIP_MAX_TARGETS; replaces any earlier target
+ *                             MATRIX (the target vector of gprhip_set_targets is a different buffer and is kept).  Allocates
+ *                             its n x k device buffers here, after comparing them with the free memory of the device:
+ *                             GPRHIP_EOOM from that comparison leaves the problem as it was
+ *                             (an allocation that fails all the same leaves it without a target matrix).
+ *   gprhip_eval_targets       l2[k]; grad_sum[n_hypers] (want_grad != 0) = gradient of the SUMMED log evidence in the order of
+ *                             gprhip_eval; coeffs (may be NULL) Fortran m x k, column j = Trained.calc_mean_coeffs of target
+ *                             j.  l_j = l1 + l2[j]; l_sum = k l1 + sum l2; dl_dsigma2_sum likewise.  h->reuse_v is honoured.
+ *   gprhip_predict_targets    means: Fortran nt x k = K_tm coeffs of the last gprhip_eval_targets (Means.calc per column).
+ *
+ * Contract
+ *   - fp64, one device: a GPRHIP_F32_BULK problem, k out of range or h->model_only = 1 -> GPRHIP_EBADARG;
+ *     gprhip_eval_targets before gprhip_set_targets_many, or gprhip_predict_targets without a completed
+ *     gprhip_eval_targets before it -> GPRHIP_ESTATE.  Nothing is evaluated in either case.
+ *   - After gprhip_eval_targets the MODEL state (U, R) is valid: gprhip_predict variances, gprhip_covariances,
+ *     gprhip_co_variance_coeffs, gprhip_condition work.  The single-target state is not: gprhip_predict MEANS and
+ *     gprhip_train_stats return GPRHIP_ESTATE until the next gprhip_eval -- never an answer for "some" column.
+ *   - gprhip_set_targets / gprhip_eval are untouched and may be interleaved with these calls on one problem.
+ *   - Every k (1 included) takes the engine row path whatever m is; results repeat bit for bit from run to run.
+ *   - The staged / sharded calls do not take several targets (their exchange-1 buffer carries one c~; its length is ABI). */
+#define GPRHIP_MAX_TARGETS 16
+int gprhip_set_targets_many(gprhip_problem* p, const double* targets, int64_t ld, int k);
+typedef struct {
+  double l1;             /* Model.calc_log_evidence (the same for every target)      */
+  double l_sum;          /* sum_j Trained.calc_log_evidence of target j              */
+  double dl_dsigma2_sum; /* sum_j calc_log_evidence_sigma2 (0 unless want_grad != 0) */
+  int64_t n_hypers;
+  int k;
+} gprhip_targets_result;
+
 /* Hyper-parameters of one evaluation.
  *   log_ell    : Cov_se_iso.Params.log_ell (ignored for Cov_se_fat)          lib/cov_se_iso.ml:23-25
  *   log_sf2    : Params.log_sf2
@@ -150,6 +188,9 @@ int64_t gprhip_n_hypers(const gprhip_problem* p, int flags);
  *   coeffs (m, may be NULL): Trained.calc_mean_coeffs (lib/fitc_gp.ml:294). */
 int gprhip_eval(gprhip_problem* p, const gprhip_hypers* h, int want_grad, gprhip_result* res,
                 double* grad, double* coeffs);
+/* Several target vectors (see gprhip_set_targets_many above). */
+int gprhip_eval_targets(gprhip_problem* p, const gprhip_hypers* h, int want_grad, gprhip_targets_result* res, double* l2,
+                        double* grad_sum, double* coeffs);
 
 /* Staged form for row-sharded evaluation across devices (one process per device).  Between the
  * stages the caller sums the exchange buffers over all shards (RCCL all-reduce on the same HIP
@@ -254,6 +295,7 @@ int gprhip_sharded_set_timing(gprhip_sharded* sp, int level);
  * The last evaluation must have had targets (model_only = 0) for the means to be meaningful. */
 int gprhip_predict(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_t nt, int predictive,
                    double* means, double* variances);
+int gprhip_predict_targets(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_t nt, double* means);
 
 /* Training-set residual statistics with the model state left by the last evaluation (which must have had
  * targets): means[i] = K_nm[i,:] . coeffs over the resident training inputs (Trained.calc_means,

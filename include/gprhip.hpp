@@ -269,6 +269,14 @@ struct Evaluation {  // everything one device evaluation returns
   bool has_grad = false;
 };
 
+struct Evaluation_many {  // gprhip_eval_targets: k target vectors (the columns of an n x k matrix) on one model
+  double l1 = 0, l_sum = 0, dl_dsigma2_sum = 0;
+  Vec l;        // k values: Trained.calc_log_evidence per target
+  Vec grad_sum; // gradient of l_sum, Hyper.get_all order
+  Mat coeffs;   // m x k: Trained.calc_mean_coeffs per column
+  bool has_grad = false;
+};
+
 struct Stats_t {  // Stats.t, lib/fitc_gp.ml:304-315
   int64_t n_samples;
   double target_variance, sse, mse, rmse, smse, msll, mad, maxad;
@@ -350,6 +358,44 @@ struct Make_deriv {
     prob.last_inducing = model.inputs.inducing.points;
     prob.state_owner = std::move(owner);
     return ev;
+  }
+
+  // Several target vectors on one model in one device evaluation (an extension beyond the reference's signature, whose
+  // Trained.t holds one target vector); the Variational flag travels in the model, so the two helpers serve every variant
+  // (what gpr_amd/fitc_gp.py calls Trained.calc_many).  `owner` as in run.
+  static Evaluation_many run_many(const Model_t& model, const Mat& targets, bool want_grad, std::shared_ptr<const void> owner) {
+    Problem& prob = *model.inputs.problem;
+    const Kernel& k = model.inputs.inducing.kernel;
+    const Mat& z = *model.inputs.inducing.points;
+    check(gprhip_set_targets_many(prob.get(), targets.data(), targets.rows, targets.cols));
+    gprhip_hypers h{};
+    Spec::fill(k, h);
+    h.sigma2 = model.sigma2;
+    h.inducing = z.data();
+    h.variational = model.variational;
+    h.model_only = 0;
+    h.jitter = cholesky_jitter;
+    h.reuse_v = (prob.last_kernel == model.kernel_ref && prob.last_inducing == model.inputs.inducing.points);
+    Evaluation_many ev;
+    ev.grad_sum.assign((size_t)std::max<int64_t>(1, gprhip_n_hypers(prob.get(), Spec::flags(k))), 0.0);
+    ev.coeffs = Mat((int)prob.m, targets.cols);
+    ev.l.assign((size_t)targets.cols, 0.0);
+    gprhip_targets_result r{};
+    check(gprhip_eval_targets(prob.get(), &h, want_grad, &r, ev.l.data(), ev.grad_sum.data(), ev.coeffs.data()));
+    for (double& v : ev.l) v += r.l1;  // (the call returns l2 per target)
+    ev.l1 = r.l1; ev.l_sum = r.l_sum; ev.dl_dsigma2_sum = r.dl_dsigma2_sum;
+    ev.has_grad = want_grad;
+    if (want_grad) ev.grad_sum.resize((size_t)r.n_hypers);
+    prob.last_kernel = model.kernel_ref;
+    prob.last_inducing = model.inputs.inducing.points;
+    prob.state_owner = std::move(owner);
+    return ev;
+  }
+  // Means.calc per target column at the points of `in` (nt x k), from the state run_many left on the model's problem
+  static Mat means_many(const Model_t& model, const Inputs_t& in, int k) {
+    Mat means(in.points->cols, k);
+    check(gprhip_predict_targets(model.inputs.problem->get(), in.points->data(), in.points->rows, in.points->cols, means.data()));
+    return means;
   }
 
   template <bool Variational, int CovKind /* 0 FITC, 1 FIC */>
