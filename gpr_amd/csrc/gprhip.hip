@@ -245,6 +245,7 @@ struct gprhip_problem {
   int tg_k = 0;               // columns of the target matrix held (0: none)
   int multi = 0;              // the evaluation in flight is one over `multi` target vectors: it takes the engine row path
   bool multi_state = false;   // the completed evaluation was one: t / w are not those of one target vector
+  bool tg_coeffs = false;     // T of that evaluation is resident in tg_small (a target matrix of another width re-makes it)
   double *tg_y = nullptr, *tg_w = nullptr;  // Y and W_mat, column-major [k][nchunks * chunk]
   double* tg_small = nullptr;  // [y2 (16) | |b_k|^2 (16) | T | T~ | B | c~ (mp x 16 each)]
   double *tg_part = nullptr, *tg_rowpart = nullptr;  // per-workgroup partials of the tall-skinny products / of the row kernels
@@ -753,6 +754,7 @@ void do_pass1(gprhip_problem* p, const gprhip_hypers* h, int want_grad, int64_t 
   // the state of the previous evaluation is void from here on; finish() re-validates it
   p->have_model = p->have_factors = false;
   p->multi_state = false;
+  p->tg_coeffs = false;
   p->stage = 0;
   p->x_last = nullptr;
   p->cond_km = -1.0;
@@ -2055,6 +2057,8 @@ void do_set_targets_many(gprhip_problem* p, const double* targets, int64_t ld, i
       q = nullptr;
     };
     release(p->tg_y); release(p->tg_w); release(p->tg_small); release(p->tg_part); release(p->tg_rowpart);
+    // (the coefficient block went with tg_small.  multi_state stays: the single-target t / w are no more valid than before)
+    p->tg_coeffs = false;
     p->alloc_bytes -= p->tg_bytes;
     p->tg_k = 0;
     p->tg_bytes = 0;
@@ -2105,6 +2109,7 @@ void do_eval_targets(gprhip_problem* p, const gprhip_hypers* h, int want_grad, g
   }
   p->multi = 0;
   p->multi_state = true;
+  p->tg_coeffs = true;
   const int m = p->m;
   std::vector<double> hs(2 * TG_LD + (size_t)p->mp * TG_LD);
   GPR_HIP(hipMemcpy(hs.data(), p->tg_small, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -2130,8 +2135,10 @@ void do_eval_targets(gprhip_problem* p, const gprhip_hypers* h, int want_grad, g
 // Means.calc (lib/fitc_gp.ml:418-425) per target column: means = K_tm T, test points in chunks of the training chunk
 void do_predict_targets(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_t nt, double* means) {
   need_model(p, "gprhip_predict_targets");
-  if (!p->multi_state || !p->tg_k) {
-    set_error("gprhip_predict_targets: the last evaluation on this problem was not a gprhip_eval_targets");
+  if (!p->multi_state || !p->tg_coeffs || !p->tg_k) {
+    set_error(p->multi_state ? "gprhip_predict_targets: gprhip_set_targets_many changed the number of target vectors after the "
+                               "last gprhip_eval_targets: its coefficients are gone"
+                             : "gprhip_predict_targets: the last evaluation on this problem was not a gprhip_eval_targets");
     throw HipFail{ST_STATE};
   }
   GPR_HIP(hipSetDevice(p->device));

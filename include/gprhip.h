@@ -119,6 +119,9 @@ int gprhip_set_targets_device(gprhip_problem* p, const double* d_targets);
  *   - fp64, one device: a GPRHIP_F32_BULK problem, k out of range or h->model_only = 1 -> GPRHIP_EBADARG;
  *     gprhip_eval_targets before gprhip_set_targets_many, or gprhip_predict_targets without a completed
  *     gprhip_eval_targets before it -> GPRHIP_ESTATE.  Nothing is evaluated in either case.
+ *   - gprhip_set_targets_many with the k of the last gprhip_eval_targets keeps that evaluation's coefficients for
+ *     gprhip_predict_targets; with another k it discards them, and gprhip_predict_targets returns GPRHIP_ESTATE until the
+ *     next gprhip_eval_targets (gprhip_predict means and gprhip_train_stats go on refusing as below).
  *   - After gprhip_eval_targets the MODEL state (U, R) is valid: gprhip_predict variances, gprhip_covariances,
  *     gprhip_co_variance_coeffs, gprhip_condition work.  The single-target state is not: gprhip_predict MEANS and
  *     gprhip_train_stats return GPRHIP_ESTATE until the next gprhip_eval -- never an answer for "some" column.

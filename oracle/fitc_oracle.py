@@ -561,19 +561,27 @@ def model_prepare_hyper(cm):
     return dict(cm=cm, v_vec=v_vec, w_mat=_F(w_mat), x_mat=_F(x_mat))
 
 
-def trained_prepare_hyper(tr):
-    """Trained.prepare_hyper lib/fitc_gp.ml:1192-1207."""
+def trained_prepare_hyper(tr, us=None, u1tu1=None):
+    """Trained.prepare_hyper lib/fitc_gp.ml:1192-1207.  us = calc_us_mat(model) and u1tu1 = the upper triangle of the
+    v1-weighted U^T U depend on the model only: a caller with several target vectors on one model passes them in."""
     cm = tr["common_model"]
     model = cm["eval_model"]
-    u_mat, x_mat = calc_us_mat(model)
+    u_mat, x_mat = calc_us_mat(model) if us is None else us
     t_vec = tr["coeffs"]
     w_mat = np.triu(cm["t_mat"]) - np.triu(np.outer(t_vec, t_vec))  # syr ~alpha:-1
-    u1 = u_mat * np.sqrt(cm_calc_v1_vec(cm))[:, None]
-    w_mat = w_mat - np.triu(u1.T @ u1)  # syrk ~trans:`T ~alpha:-1
+    if u1tu1 is None:
+        u1tu1 = model_u1tu1(cm, u_mat)
+    w_mat = w_mat - u1tu1  # syrk ~trans:`T ~alpha:-1
     u2 = u_mat * tr["w_vec"][:, None]
     w_mat = w_mat + np.triu(u2.T @ u2)
     x_mat = x_mat - u_mat * tr["v_vec"][:, None] - np.outer(tr["w_vec"], t_vec)  # axpy, ger
     return dict(cm=cm, v_vec=tr["v_vec"], w_mat=_F(w_mat), x_mat=_F(x_mat))
+
+
+def model_u1tu1(cm, u_mat):
+    """triu(U1^T U1), U1 = diag(sqrt v1) U: the model's share of W in Trained.prepare_hyper (lib/fitc_gp.ml:1196-1199)."""
+    u1 = u_mat * np.sqrt(cm_calc_v1_vec(cm))[:, None]
+    return np.triu(u1.T @ u1)
 
 
 def symm2_trace(a, b):
@@ -812,20 +820,46 @@ def evaluate(k, inducing_points, inputs, targets, sigma2, variational=False,
 # 2+d*m hypers in Python is too slow (cpu_baseline leg, mid-size parity tests).
 # Validated against `evaluate` in tests/test_oracle.py.
 # ---------------------------------------------------------------------------
-def evaluate_fast(k, inducing_points, inputs, targets, sigma2, variational=False):
+def _fast_model(k, inducing_points, inputs, sigma2, variational):
+    """The part of evaluate_fast that depends on the model only: covariances, both factorisations, Common_model, and the
+    model's share of Trained.prepare_hyper."""
     inducing_points = _F(inducing_points)
     inputs = _F(inputs)
-    targets = np.asarray(targets, dtype=np.float64)
     n = inputs.shape[1]
-    d, m = inducing_points.shape
     km, shared_upper = spec_calc_shared_upper(k, inducing_points)
     inducing = inducing_calc_internal(k, inducing_points, km)
     knm, shared_cross = spec_calc_shared_cross(k, inputs, inducing_points)
     kn_diag = spec_calc_diag(k, n)
     model = model_calc_with_kn_diag(inducing, knm, sigma2, kn_diag, variational)
     cm = cm_calc(model)
+    us = calc_us_mat(model)
+    return dict(k=k, inducing_points=inducing_points, km=km, shared_upper=shared_upper, knm=knm, shared_cross=shared_cross,
+                model=model, cm=cm, us=us, u1tu1=model_u1tu1(cm, us[0]))
+
+
+def evaluate_fast(k, inducing_points, inputs, targets, sigma2, variational=False):
+    return _fast_target(_fast_model(k, inducing_points, inputs, sigma2, variational), targets)
+
+
+def evaluate_fast_many(k, inducing_points, inputs, targets, sigma2, variational=False):
+    """evaluate_fast for every column of the n x K matrix `targets` on ONE model: the n m^2 model work runs once, each column
+    adds Deriv Trained.calc, Trained.prepare_hyper and the vectorised gradient -- the statements evaluate_fast runs, on the
+    same operands in the same order.  Returns the list of per-column dicts."""
+    targets = np.asarray(targets, dtype=np.float64)
+    if targets.ndim != 2:
+        raise ValueError("evaluate_fast_many: targets must be n x K")
+    mp = _fast_model(k, inducing_points, inputs, sigma2, variational)
+    return [_fast_target(mp, np.ascontiguousarray(targets[:, c])) for c in range(targets.shape[1])]
+
+
+def _fast_target(mp, targets):
+    """The per-target part of evaluate_fast on the model part `mp`."""
+    k, inducing_points, km, shared_upper = mp["k"], mp["inducing_points"], mp["km"], mp["shared_upper"]
+    knm, shared_cross, model, cm = mp["knm"], mp["shared_cross"], mp["model"], mp["cm"]
+    targets = np.asarray(targets, dtype=np.float64)
+    d, m = inducing_points.shape
     tr = deriv_trained_calc(cm, targets)
-    ht = trained_prepare_hyper(tr)
+    ht = trained_prepare_hyper(tr, us=mp["us"], u1tu1=mp["u1tu1"])
     v_vec, w_mat, x_mat = ht["v_vec"], ht["w_mat"], ht["x_mat"]
     out = dict(l1=model["l1"], l2=tr["l2"], l=tr["l"], coeffs=tr["coeffs"],
                dl_dsigma2=common_calc_log_evidence_sigma2(cm, tr["v_vec"]))

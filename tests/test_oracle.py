@@ -495,3 +495,47 @@ def test_oracle_fat_gradient_against_80_bit_central_differences():
         got = ref["grad"][hyp.index(name)]
         assert abs(got - g) <= 1e-8 * scale, (name, got, g)
     assert abs(ref["dl_dsigma2"] - fd(s2=None)) <= 1e-8 * max(1.0, abs(ref["dl_dsigma2"]))
+
+
+def _many_case(kind):
+    """(oracle kernel, Z, X, n x 4 targets): Cov_se_iso, or Cov_se_fat with projection, heteroskedastic noise and multiscales"""
+    rng = np.random.default_rng(21)
+    n, m, K = 700, 150, 4
+    D = 3 if kind == "iso" else 6
+    X = np.asfortranarray(rng.normal(size=(D, n)))
+    s = X.sum(0)
+    Y = np.asfortranarray(np.stack([np.sin((0.4 + 0.2 * c) * s + c) + (0.05 + 0.03 * c) * rng.normal(size=n) for c in range(K)],
+                                   axis=1))
+    pick = rng.permutation(n)[:m]
+    if kind == "iso":
+        k = O.SeIsoKernel(0.5 * np.log(D), 0.0)
+        Z = np.asfortranarray(X[:, pick] + 0.01 * rng.normal(size=(D, m)))
+    else:
+        d = 3
+        k = O.SeFatKernel(d, 0.1, 0.5 * rng.normal(size=(D, d)), np.full(m, -5.0) + 0.1 * rng.normal(size=m),
+                          -0.7 + 0.2 * rng.normal(size=(d, m)))
+        Z = np.asfortranarray(O.se_fat_project(k, X[:, pick]) + 0.01 * rng.normal(size=(d, m)))
+    return k, Z, X, Y
+
+
+@pytest.mark.parametrize("variational", [False, True], ids=["standard", "variational"])
+@pytest.mark.parametrize("kind", ["iso", "fat_all"])
+def test_evaluate_fast_many_is_evaluate_fast_per_column(kind, variational):
+    """evaluate_fast_many shares the model part of evaluate_fast between the columns; the per-column statements are the same
+    ones on the same operands in the same order, so every result is bit for bit that of evaluate_fast on that column."""
+    k, Z, X, Y = _many_case(kind)
+    many = O.evaluate_fast_many(k, Z, X, Y, 0.1, variational=variational)
+    assert len(many) == Y.shape[1]
+    for c, got in enumerate(many):
+        one = O.evaluate_fast(k, Z, X, Y[:, c], 0.1, variational=variational)
+        assert set(got) == set(one)
+        assert got["l1"] == one["l1"] and got["l2"] == one["l2"] and got["l"] == one["l"]
+        assert got["dl_dsigma2"] == one["dl_dsigma2"]
+        assert np.array_equal(got["coeffs"], one["coeffs"]) and np.array_equal(got["grad"], one["grad"])
+    # the columns differ: a result copied from one column to the others would not pass as parity anywhere
+    assert not np.array_equal(many[0]["grad"], many[1]["grad"])
+    # ... and the one-column call is still pinned against the reference-order evaluation
+    ref = O.evaluate(k, Z, X, Y[:, 2], 0.1, variational=variational)
+    assert abs(many[2]["l"] - ref["l"]) <= 1e-12 * abs(ref["l"]) and relinf(many[2]["grad"], ref["grad"]) < 1e-9
+    with pytest.raises(ValueError):
+        O.evaluate_fast_many(k, Z, X, Y[:, 0], 0.1)
