@@ -266,6 +266,8 @@ struct gprhip_problem {
   bool use_mid() const {
     return !multi && mid_path && !f32 && !engine_steps && !use_small() && mid_path_fits(m, mp, d, has_proj() ? D : 0, n, has_ms());
   }
+  // two tiles whose Gram accumulations go through mid.hip's own launch pair (else: through the engine's launch)
+  bool mid_pair() const { return use_mid() && mp > TILE && use_mid_gram(); }
 };
 
 namespace {
@@ -739,163 +741,230 @@ void targets_xcorr(gprhip_problem* p, double* X, int64_t base, int rows) {
   tstop(p);
 }
 
+// ---- the two exchange buffers by part (gprhip_exchange_len has the lengths)
+// exchange 1: [packed upper tiles of B~_part | c~ (mp) | scalar tail (A1_TAIL)]
+template <typename T> struct Ex1 { T *tiles, *c, *tail; };
+template <typename T> Ex1<T> ex1_of(const gprhip_problem* p, T* ar1) {
+  T* c = ar1 + packed_upper_len(p->mp);
+  return {ar1, c, c + p->mp};
+}
+// exchange 2: [packed upper tiles of G~_part | column block (col_rows x mp) | `Proj second term (D x d) | scalar tail (A2_TAIL)]
+// The host mirror (ex_host + A1_TAIL) starts at the column block: ex2_proj_off / ex2_tail_off count from there.
+int64_t ex2_proj_off(const gprhip_problem* p) { return p->col_rows() * p->mp; }
+int64_t ex2_tail_off(const gprhip_problem* p) { return ex2_proj_off(p) + (int64_t)p->dbig() * p->d; }
+template <typename T> struct Ex2 {
+  T *tiles, *col, *proj, *tail;
+  int64_t len_from_col() const { return (tail + A2_TAIL) - col; }  // what the host assembly reads after a gradient evaluation
+};
+template <typename T> Ex2<T> ex2_of(const gprhip_problem* p, T* ar2) {
+  T* col = ar2 + packed_upper_len(p->mp);
+  return {ar2, col, col + ex2_proj_off(p), col + ex2_tail_off(p)};
+}
+
+// ---- scratch of an evaluation: everything its path allocates lazily, at the first evaluation that needs it (pass 1, once
+// the path is known; pass 2 and the finish stage allocate nothing)
 template <typename TS>
-void do_pass1(gprhip_problem* p, const gprhip_hypers* h, int want_grad, int64_t n_total, double* ar1) {
-  if (!h || !h->inducing) {
-    set_error("gprhip: hypers/inducing pointer is NULL");
-    throw HipFail{ST_BAD_ARG};
-  }
-  if (!p->have_inputs || (!p->have_targets && !h->model_only)) {
-    set_error("gprhip: inputs/targets not set");
-    throw HipFail{ST_STATE};
-  }
-  GPR_HIP(hipSetDevice(p->device));
-  hipStream_t s = p->stream;
-  // the state of the previous evaluation is void from here on; finish() re-validates it
-  p->have_model = p->have_factors = false;
-  p->multi_state = false;
-  p->tg_coeffs = false;
-  p->stage = 0;
-  p->x_last = nullptr;
-  p->cond_km = -1.0;
-  upload_hypers(p, h);
-  p->want_grad = want_grad;
-  p->n_total = n_total;
+void ensure_eval_scratch(gprhip_problem* p, bool small, bool mid, bool reuse) {
   const int mp = p->mp;
-  const int64_t mm = (int64_t)mp * mp;
-  double* ar1_c = ar1 + packed_upper_len(mp);
-  double* ar1_tail = ar1_c + mp;
   if (!p->Vstore)  // V = K U^-1 for all rows of the shard stays resident (one SYRK launch; pass 2 re-reads it)
     p->Vstore = p->alloc<TS>((int64_t)p->nchunks * p->chunk * mp);
-  TS* const Vstore = static_cast<TS*>(p->Vstore);
-  TS* const bufA = static_cast<TS*>(p->bufA);
-  TS* const slices = static_cast<TS*>(p->slices);
-  // K resident (see Kstore): decided at the first gradient evaluation that can use it, kept for the problem's life
-  const bool small = p->use_small();
-  const bool mid = p->use_mid();
-  if (small && !p->small_part) p->small_part = p->alloc<double>(small_part_len(p->d, p->D));
-  if (mid && !p->mid_part) p->mid_part = p->alloc<double>(mid_part_len(mp, p->d, p->D));
-  if (!p->Kstore && !p->kstore_tried && !small && !mid && want_grad && p->k_resident && p->kind == GPRHIP_COV_SE_FAT && h->tproj &&
-      !h->log_multiscales_m05 && p->d <= 64 && p->D <= 64 && !p->grad_scalar) {
-    p->kstore_tried = true;
-    size_t free_b = 0, total_b = 0;
-    const size_t need = (size_t)p->nchunks * p->chunk * mp * sizeof(TS);
-    // taken only while it leaves 4 GB free AND stays below 40 % of the device's memory: the copy is held for the life of
-    // the problem, and other problems (fitc_gp caches several per functor; other shards may share the device) must still
-    // find room.  GPRHIP_K_RESIDENT=0 never keeps it.
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > need + (size_t(4) << 30) && need <= total_b / 5 * 2) {
-      void* ptr = nullptr;
-      if (hipMalloc(&ptr, need) == hipSuccess) {
-        p->allocs.push_back(ptr);
-        p->Kstore = ptr;
-      } else {
-        (void)hipGetLastError();  // no room after all: the gradient kernel recomputes K
-      }
+  if (small) {
+    if (!p->small_part) p->small_part = p->alloc<double>(small_part_len(p->d, p->D));
+    if (!reuse && !p->small_k && p->d <= 8 && !p->has_ms()) p->small_k = p->alloc<double>(round_up(p->n, TILE) * 64);
+  }
+  if (mid) {
+    if (!p->mid_part) p->mid_part = p->alloc<double>(mid_part_len(mp, p->d, p->D));
+    if (p->mid_pair() && !p->mid_gram_part) p->mid_gram_part = p->alloc<double>(mid_gram_part_len());
+    if (p->want_grad && !p->mid_done) {  // (every finish launch pair leaves the counter at zero again)
+      p->mid_done = p->alloc<int>(1);
+      GPR_HIP(hipMemsetAsync(p->mid_done, 0, sizeof(int), p->stream));
     }
   }
-  TS* const Kstore = static_cast<TS*>(p->Kstore);
+  if (!small && !mid && p->want_grad && p->has_ms() && p->has_proj() && !p->rowes) {
+    const int nslots = 4 * ((mp + 255) / 256);  // (as the gradient kernels of pass 2 lay them out)
+    p->rowes = p->alloc<double>(p->chunk * nslots * p->d);
+    p->es2 = p->alloc<double>(p->chunk * p->d);
+  }
+}
 
-  const bool reuse = h->reuse_v != 0;
-  if (reuse && !p->have_v) {
-    set_error("gprhip: reuse_v set but this problem holds no V of a previous evaluation");
-    throw HipFail{ST_STATE};
+// K resident (see Kstore): decided at the first gradient evaluation that can use it, kept for the problem's life.  An
+// attempt that finds no room fails silently: the gradient kernel then recomputes K.
+template <typename TS>
+void try_k_resident(gprhip_problem* p) {
+  if (p->Kstore || p->kstore_tried || !p->want_grad || !p->k_resident || !p->has_proj() || p->has_ms() || p->d > 64 || p->D > 64 ||
+      p->grad_scalar)
+    return;
+  p->kstore_tried = true;
+  size_t free_b = 0, total_b = 0;
+  const size_t need = (size_t)p->nchunks * p->chunk * p->mp * sizeof(TS);
+  // taken only while it leaves 4 GB free AND stays below 40 % of the device's memory: the copy is held for the life of
+  // the problem, and other problems (fitc_gp caches several per functor; other shards may share the device) must still
+  // find room.  GPRHIP_K_RESIDENT=0 never keeps it.
+  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > need + (size_t(4) << 30) && need <= total_b / 5 * 2) {
+    void* ptr = nullptr;
+    if (hipMalloc(&ptr, need) == hipSuccess) {
+      p->allocs.push_back(ptr);
+      p->Kstore = ptr;
+    } else {
+      (void)hipGetLastError();  // no room after all: the gradient kernel recomputes K
+    }
   }
-  p->have_v = false;
-  if (!reuse) p->have_k = p->small_k_valid = false;
-  // K_nm of the first chunk does not depend on U: it is built on the second stream while the (latency-bound, few-CU)
-  // factorisation and inversion of K_m run -- 0.4 ms of every evaluation, which is what a chunk's builder takes.
-  // (Not under the per-stage timer, whose events sit on the main stream.)
-  const bool cov0_ahead = !reuse && !p->timer.on && !small && !mid;
-  if (cov0_ahead) {
-    GPR_HIP(hipEventRecord(p->ev_fork, s));  // hypers, inducing points and projections are enqueued on s
-    GPR_HIP(hipStreamWaitEvent(p->stream2, p->ev_fork, 0));
-    cov_chunk<TS>(p, 0, Kstore ? Kstore : bufA, p->stream2);
-    GPR_HIP(hipEventRecord(p->ev_join, p->stream2));
+}
+
+// Level-1 timer: an event pair around the dominant kernel alone (the pass-1 Gram launch).
+template <typename F>
+void kernel_timed(gprhip_problem* p, bool timed, F&& launch) {
+  timed = timed && p->timer.kernel;
+  if (timed) {
+    if (!p->timer.k0) {
+      GPR_HIP(hipEventCreate(&p->timer.k0));
+      GPR_HIP(hipEventCreate(&p->timer.k1));
+    }
+    GPR_HIP(hipEventRecord(p->timer.k0, p->stream));
   }
+  launch();
+  if (timed) {
+    GPR_HIP(hipEventRecord(p->timer.k1, p->stream));
+    p->timer.k_recorded = true;
+  }
+}
+
+// The Gram accumulation over all rows of the shard (V is resident), reduced into the packed upper tiles of an exchange
+// buffer:
+//   pass 1:  B~_part = V^T diag(is) V  (R~^T R~ replaces the stacked QR's R, lib/fitc_gp.ml:170-182) into exchange 1, and
+//            c~ = V^T (is .* y) into `csum`;
+//   pass 2:  G~_part = V^T diag(v) V  (the two dsyrk of lib/fitc_gp.ml:1198-1203, whitened, in one) into exchange 2.
+// mid_pair: by mid.hip's Gram launch pair (two tiles; the engine's SYRK-shaped launch, its column-sum reduction and its
+// slice sum cost 45 us at these sizes whatever the row count); else one SYRK-shaped engine launch + its reductions.
+template <typename TS>
+void gram_over_v(gprhip_problem* p, int pass, bool mid_pair, double* tiles, double* csum) {
+  hipStream_t s = p->stream;
+  const int mp = p->mp;
+  const bool p1 = pass == 1;
+  tstart(p, p1 ? "p1_syrk_B" : "p2_syrk_W");
+  if (mid_pair) {
+    MidGramArgs ga;
+    ga.V = static_cast<const double*>(p->Vstore); ga.w = p1 ? p->is : p->v; ga.y = p1 ? p->yis : nullptr; ga.rows = (int)p->n;
+    ga.part = p->mid_gram_part;
+    // (the level-1 bracket goes around a fresh evaluation's launch; a re-weighted one has never carried it)
+    kernel_timed(p, p1 && !p->h.reuse_v, [&] { launch_mid_gram(ga, tiles, p1 ? csum : nullptr, s); });
+    tstop(p);
+    return;
+  }
+  const int64_t mm = (int64_t)mp * mp, ktot = p->rows_total_padded();
+  TS* const Vstore = static_cast<TS*>(p->Vstore);
+  TS* const slices = static_cast<TS*>(p->slices);
+  const int ks = p1 ? pick_kslices(mp, ktot, p->kslices, p->slice_rows, !p->f32) : p->ks_used;
+  GemmArgsT<TS> g;
+  g.A = Vstore; g.lda = mp; g.B = Vstore; g.ldb = mp; g.C = slices; g.ldc = mp;
+  g.M = mp; g.N = mp; g.K = (int)ktot; g.beta = 0.0; g.upper_only = 1;
+  g.scale_k = p1 ? row_weights<TS>(p, p->is, p->is_f) : row_weights<TS>(p, p->v, p->v_f);
+  g.kslices = ks; g.slice_stride = mm;
+  // The pass-2 launch goes through the kernel of the pass-1 one (its diagonal tiles then also form column sums nobody
+  // reads): measured in round 4, the plain weighted kernel (gemm_*_tn_w) runs this very launch with 172 GB instead of
+  // 67 GB through the fabric and 1-2 ms slower on most boxes of the pool -- its workgroups fall out of step from the
+  // first residency round on -- while the column-sum kernel does not (tools/lab19.sh, lab20.sh; GPRHIP_W_AS_WS=0 restores
+  // the plain kernel).
+  const bool colsums = p1 || p->w_as_ws != 0;
+  if (colsums) {
+    // pass 1: c~ rides along -- the diagonal-tile blocks of every k-slice also sum V[k][c] * (is*y)[k] over their rows
+    g.cs_w = p1 ? row_weights<TS>(p, p->yis, p->yis_f) : g.scale_k;
+    g.cs_out = p->gemvpart;
+  }
+  kernel_timed(p, p1, [&] { launch_gemm(OP_TN, g, s); });
+  const int ksd = gemm_syrk_diag_slices(ks, !p->f32, colsums);  // the diagonal tiles (which also store the column sums) use fewer, longer slices
+  if (p1) launch_reduce_rows(p->gemvpart, ksd, mp, csum, 1, s);
+  tstop(p);
+  if (p1) p->ks_used = ks;
+  launch_sum_slices<TS>(nullptr, slices, ks, mm, mp, tiles, s, 1, ksd);
+}
+
+// ---- pass 1
+// K_nm of the first chunk does not depend on U: it is built on the second stream while the (latency-bound, few-CU)
+// factorisation and inversion of K_m run -- 0.4 ms of every evaluation, which is what a chunk's builder takes.
+// (Not under the per-stage timer, whose events sit on the main stream.)
+template <typename TS>
+void fork_first_cov(gprhip_problem* p) {
+  GPR_HIP(hipEventRecord(p->ev_fork, p->stream));  // hypers, inducing points and projections are enqueued on the main stream
+  GPR_HIP(hipStreamWaitEvent(p->stream2, p->ev_fork, 0));
+  cov_chunk<TS>(p, 0, static_cast<TS*>(p->Kstore ? p->Kstore : p->bufA), p->stream2);
+  GPR_HIP(hipEventRecord(p->ev_join, p->stream2));
+}
+
+// U = chol(K_m + jitter) and U^-1.  clear_c: c~ and the tail of exchange 1 are accumulated into by this evaluation's row
+// pass (the small and the one-tile passes write them outright)
+void pass1_km_chol(gprhip_problem* p, const Ex1<double>& ex, bool clear_c) {
+  hipStream_t s = p->stream;
+  const int mp = p->mp;
   tstart(p, "km_chol");
   // the scalars and the two potrf flags behind them (single-block problems: every slot an evaluation reads is written by
   // the factorisation kernels themselves, flags included), and the accumulators of the exchange-1 tail (the small row pass
   // writes them outright)
   if (mp != TILE || p->engine_steps) GPR_HIP(hipMemsetAsync(p->scal, 0, (NSCAL + 2) * sizeof(double), s));
-  // (the one-tile passes write c~ and the tail outright; with two tiles c~ still comes from the engine's launch, accumulated)
-  if (!(small || (mid && mp == TILE)) || reuse) GPR_HIP(hipMemsetAsync(ar1_c, 0, (size_t)(mp + A1_TAIL) * sizeof(double), s));
+  // (the one-tile passes write c~ and the tail outright; with two tiles c~ still comes from the Gram launch, accumulated)
+  if (clear_c) GPR_HIP(hipMemsetAsync(ex.c, 0, (size_t)(mp + A1_TAIL) * sizeof(double), s));
   // K_m + (hetero) + jitter goes straight into the factor's buffer (kj is scratch of the finish stage only)
   // (tried for 65 .. 128 inducing points too, round 6: 16 384 entries on ONE CU cost 20 us at d = 8 where the cov_upper launch
   //  spread over the chip costs 4 + its 4 us gap -- K_m phase 45 -> 68 us; it stays a launch of its own above 64)
   if (mp == TILE && p->m <= 64 && p->d <= 16 && !p->engine_steps && !p->has_ms() && p->small_path) {
     PotrfKm g;  // few inducing points: the covariance is built inside the factorisation kernel (chol.hip, MODE 2)
-    g.cp = p->cp; g.Z = p->Z; g.m = p->m; g.d = p->d; g.jitter = h->jitter;
+    g.cp = p->cp; g.Z = p->Z; g.m = p->m; g.d = p->d; g.jitter = p->h.jitter;
     g.het = p->has_het() ? p->het : nullptr; g.km = p->km;
     launch_potrf_km(g, p->umat, p->uinv, p->info, s);
   } else {
-    launch_cov_upper(p->cp, p->Z, p->m, mp, p->d, h->jitter, p->has_het() ? p->het : nullptr, p->km, p->umat, s);
+    launch_cov_upper(p->cp, p->Z, p->m, mp, p->d, p->h.jitter, p->has_het() ? p->het : nullptr, p->km, p->umat, s);
     potrf_trtri(p, p->umat, p->uinv, p->wmat, p->info);  // U = chol(K_m + jitter), lib/fitc_gp.ml:53-57, and U^-1
   }
-  if (p->f32) launch_to_float(p->uinv, p->uinv_f, mm, s);
+  if (p->f32) launch_to_float(p->uinv, p->uinv_f, (int64_t)mp * mp, s);
   tstop(p);
+}
 
-  if constexpr (std::is_same<TS, double>::value) {
-    if (small && !reuse) {
-      // at most 64 inducing points: covariance, V, the row quantities and both accumulations in one kernel + one reduction
-      // (small.hip)
-      tstart(p, "p1_small");
-      SmallPass1Args a;
-      a.cp = p->cp; a.pts = p->pts(); a.Z = p->Z; a.uinv = p->uinv; a.y = h->model_only ? nullptr : p->y;
-      a.rows = (int)p->n; a.rows_p = (int)round_up(p->n, TILE); a.m = p->m; a.mp = mp; a.d = p->d;
-      a.sigma2 = h->sigma2;
-      a.V = Vstore; a.r = p->r; a.is = p->is; a.yis = p->yis; a.part = p->small_part;
-      if (!p->small_k && p->d <= 8 && !p->has_ms()) p->small_k = p->alloc<double>((int64_t)a.rows_p * 64);
-      a.Kout = (p->d <= 8 && !p->has_ms()) ? p->small_k : nullptr;
-      launch_small_pass1(a, ar1, ar1_c, ar1_tail, s);
-      p->small_k_valid = a.Kout != nullptr;
-      tstop(p);
-      p->stage = 1;
-      p->have_v = true;
-      p->have_k = false;
-      return;
-    }
-    if (mid && !reuse) {
-      // one or two 128-column tiles of inducing points: the same in one kernel per row block with the triangular operand
-      // streamed from memory (mid.hip); with two tiles the accumulations B~ and c~ stay with the engine's launch below
-      tstart(p, "p1_mid");
-      MidPass1Args a;
-      a.cp = p->cp; a.pts = p->pts(); a.Z = p->Z; a.uinv = p->uinv; a.y = h->model_only ? nullptr : p->y;
-      a.rows = (int)p->n; a.rows_p = (int)round_up(p->n, TILE); a.m = p->m; a.mp = mp; a.d = p->d;
-      a.sigma2 = h->sigma2;
-      a.V = Vstore; a.r = p->r; a.is = p->is; a.yis = p->yis; a.part = p->mid_part;
-      launch_mid_pass1(a, ar1, ar1_c, ar1_tail, s);
-      tstop(p);
-      if (mp > TILE && p->use_mid_gram()) {
-        // two tiles: B~_part and c~ over the resident V by mid.hip's Gram launch pair (the engine's SYRK-shaped launch, its
-        // column-sum reduction and its slice sum cost 45 us at these sizes whatever the row count)
-        tstart(p, "p1_syrk_B");
-        if (!p->mid_gram_part) p->mid_gram_part = p->alloc<double>(mid_gram_part_len());
-        MidGramArgs ga;
-        ga.V = reinterpret_cast<const double*>(Vstore); ga.w = p->is; ga.y = p->yis; ga.rows = (int)p->n;
-        ga.part = p->mid_gram_part;
-        if (p->timer.kernel) {
-          if (!p->timer.k0) {
-            GPR_HIP(hipEventCreate(&p->timer.k0));
-            GPR_HIP(hipEventCreate(&p->timer.k1));
-          }
-          GPR_HIP(hipEventRecord(p->timer.k0, s));
-        }
-        launch_mid_gram(ga, ar1, ar1_c, s);
-        if (p->timer.kernel) {
-          GPR_HIP(hipEventRecord(p->timer.k1, s));
-          p->timer.k_recorded = true;
-        }
-        tstop(p);
-      }
-      if (mp == TILE || p->use_mid_gram()) {
-        p->stage = 1;
-        p->have_v = true;
-        p->have_k = false;
-        return;
-      }
-    }
-  }
-  const bool rows_done = mid && !reuse;  // (two tiles: V and the row quantities are there, the chunk loop has nothing to do)
+// the fields the one-kernel row passes of small.hip and mid.hip share
+template <typename Args>
+void fill_row_pass1(const gprhip_problem* p, Args& a) {
+  a.cp = p->cp; a.pts = p->pts(); a.Z = p->Z; a.uinv = p->uinv; a.y = p->h.model_only ? nullptr : p->y;
+  a.rows = (int)p->n; a.rows_p = (int)round_up(p->n, TILE); a.m = p->m; a.mp = p->mp; a.d = p->d;
+  a.sigma2 = p->h.sigma2;
+  a.V = static_cast<double*>(p->Vstore); a.r = p->r; a.is = p->is; a.yis = p->yis;
+}
+
+// at most 64 inducing points: covariance, V, the row quantities and both accumulations in one kernel + one reduction
+// (small.hip)
+void pass1_small(gprhip_problem* p, const Ex1<double>& ex) {
+  tstart(p, "p1_small");
+  SmallPass1Args a;
+  fill_row_pass1(p, a);
+  a.part = p->small_part;
+  a.Kout = (p->d <= 8 && !p->has_ms()) ? p->small_k : nullptr;
+  launch_small_pass1(a, ex.tiles, ex.c, ex.tail, p->stream);
+  p->small_k_valid = a.Kout != nullptr;
+  tstop(p);
+  p->have_k = false;
+}
+
+// one or two 128-column tiles of inducing points: the same in one kernel per row block with the triangular operand
+// streamed from memory (mid.hip).  One tile: that kernel accumulates B~ and c~ as well.  Two tiles: mid rows, then the Gram
+// accumulation -- by mid.hip's launch pair, or by the engine's launch (GPRHIP_MID_GRAM=0, shards above MID_GRAM_ROWS)
+void pass1_mid(gprhip_problem* p, const Ex1<double>& ex) {
+  tstart(p, "p1_mid");
+  MidPass1Args a;
+  fill_row_pass1(p, a);
+  a.part = p->mid_part;
+  launch_mid_pass1(a, ex.tiles, ex.c, ex.tail, p->stream);
+  tstop(p);
+  if (p->mp > TILE) gram_over_v<double>(p, 1, p->mid_pair(), ex.tiles, ex.c);
+  p->have_k = false;
+}
+
+// the chunked engine path: per row chunk K, V = K U^-1 and the row quantities (reuse: the row quantities alone, from the
+// resident V and r), then one Gram accumulation over all rows.  Re-weighted evaluations (reuse_v) of every path come here.
+template <typename TS>
+void pass1_engine(gprhip_problem* p, const Ex1<double>& ex, bool reuse, bool cov0_ahead) {
+  hipStream_t s = p->stream;
+  const int mp = p->mp;
+  TS* const Vstore = static_cast<TS*>(p->Vstore);
+  TS* const Kstore = static_cast<TS*>(p->Kstore);
+  TS* const bufA = static_cast<TS*>(p->bufA);
   // Overlap (GPRHIP_COV_OVERLAP=1): chunk c + 1's covariance goes out on the second stream just before chunk c's V product
   // goes out on the main one, into the other chunk buffer (pass 1 uses one of the two at a time) -- it waits only for the V
   // product that last read that buffer, i.e. it runs beside V(c).
@@ -909,7 +978,7 @@ void do_pass1(gprhip_problem* p, const gprhip_hypers* h, int want_grad, int64_t 
     if (Kstore) return Kstore + (int64_t)c * p->chunk * mp;
     return (overlap && (c & 1)) ? bufB1 : bufA;
   };
-  for (int c = 0; c < (rows_done ? 0 : p->nchunks); ++c) {
+  for (int c = 0; c < p->nchunks; ++c) {
     const int64_t rows = p->rows_of(c);
     const int rows_p = (int)round_up(rows, TILE);
     const int64_t base = (int64_t)c * p->chunk;
@@ -939,59 +1008,307 @@ void do_pass1(gprhip_problem* p, const gprhip_hypers* h, int want_grad, int64_t 
     tstart(p, "p1_rows");
     Pass1RowArgs ra;
     ra.part = reuse ? nullptr : p->rp1; ra.npart = gemm_row_parts_per_tile() * (mp / TILE); ra.ld = rows_p;
-    ra.y = h->model_only ? nullptr : p->y + base; ra.rows = (int)rows;
-    ra.sf2 = p->cp.sf2; ra.sigma2 = h->sigma2;
+    ra.y = p->h.model_only ? nullptr : p->y + base; ra.rows = (int)rows;
+    ra.sf2 = p->cp.sf2; ra.sigma2 = p->h.sigma2;
     ra.r = p->r + base; ra.is = p->is + base; ra.yis = p->yis + base; ra.partial = p->rowpart;
     launch_pass1_rows(ra, s);
-    launch_reduce_rows(p->rowpart, pass1_row_blocks(rows_p), 4, ar1_tail, 1, s);
+    launch_reduce_rows(p->rowpart, pass1_row_blocks(rows_p), 4, ex.tail, 1, s);
     tstop(p);
   }
-  if (mid && reuse && mp > TILE && p->use_mid_gram()) {
-    // Model.update_sigma2 on a two-tile problem whose fresh evaluations accumulate B~ with mid.hip's launch pair: the same
-    // pair here, so that the re-weighted evaluation returns the very numbers a fresh one would
-    // (test_update_sigma2_reuses_resident_v)
-    tstart(p, "p1_syrk_B");
-    if (!p->mid_gram_part) p->mid_gram_part = p->alloc<double>(mid_gram_part_len());
-    MidGramArgs ga;
-    ga.V = reinterpret_cast<const double*>(Vstore); ga.w = p->is; ga.y = p->yis; ga.rows = (int)p->n;
-    ga.part = p->mid_gram_part;
-    launch_mid_gram(ga, ar1, ar1_c, s);
-    tstop(p);
-    p->stage = 1;
-    p->have_v = true;
-    return;
+  // Model.update_sigma2 on a two-tile problem whose fresh evaluations accumulate B~ with mid.hip's launch pair: the same
+  // pair here, so that the re-weighted evaluation returns the very numbers a fresh one would
+  // (test_update_sigma2_reuses_resident_v)
+  gram_over_v<TS>(p, 1, reuse && p->mid_pair(), ex.tiles, ex.c);
+  if (!reuse) p->have_k = Kstore != nullptr;
+}
+
+template <typename TS>
+void do_pass1(gprhip_problem* p, const gprhip_hypers* h, int want_grad, int64_t n_total, double* ar1) {
+  if (!h || !h->inducing) {
+    set_error("gprhip: hypers/inducing pointer is NULL");
+    throw HipFail{ST_BAD_ARG};
   }
-  // one SYRK-shaped launch over all rows of the shard (V is resident): B~_part = V^T diag(is) V
-  // (R~^T R~ replaces the stacked QR's R, lib/fitc_gp.ml:170-182), and c~ = V^T (is .* y)
-  const int64_t ktot = p->rows_total_padded();
-  const int ks = pick_kslices(mp, ktot, p->kslices, p->slice_rows, !p->f32);
-  tstart(p, "p1_syrk_B");
-  GemmArgsT<TS> b;
-  b.A = Vstore; b.lda = mp; b.B = Vstore; b.ldb = mp; b.C = slices; b.ldc = mp;
-  b.M = mp; b.N = mp; b.K = (int)ktot; b.beta = 0.0; b.scale_k = row_weights<TS>(p, p->is, p->is_f); b.upper_only = 1;
-  b.kslices = ks; b.slice_stride = mm;
-  // c~ rides along: the diagonal-tile blocks of every k-slice also sum V[k][c] * (is*y)[k] over their rows
-  b.cs_w = row_weights<TS>(p, p->yis, p->yis_f); b.cs_out = p->gemvpart;
-  if (p->timer.kernel) {
-    if (!p->timer.k0) {
-      GPR_HIP(hipEventCreate(&p->timer.k0));
-      GPR_HIP(hipEventCreate(&p->timer.k1));
-    }
-    GPR_HIP(hipEventRecord(p->timer.k0, s));
+  if (!p->have_inputs || (!p->have_targets && !h->model_only)) {
+    set_error("gprhip: inputs/targets not set");
+    throw HipFail{ST_STATE};
   }
-  launch_gemm(OP_TN, b, s);
-  if (p->timer.kernel) {
-    GPR_HIP(hipEventRecord(p->timer.k1, s));
-    p->timer.k_recorded = true;
+  GPR_HIP(hipSetDevice(p->device));
+  // the state of the previous evaluation is void from here on; finish() re-validates it
+  p->have_model = p->have_factors = false;
+  p->multi_state = false;
+  p->tg_coeffs = false;
+  p->stage = 0;
+  p->x_last = nullptr;
+  p->cond_km = -1.0;
+  upload_hypers(p, h);
+  p->want_grad = want_grad;
+  p->n_total = n_total;
+  const bool reuse = h->reuse_v != 0;
+  // the path of this evaluation.  A re-weighted one (reuse_v) has V and r already: whichever path made them, its rows go
+  // through the engine's row kernel
+  const bool small = p->use_small(), mid = p->use_mid();
+  ensure_eval_scratch<TS>(p, small, mid, reuse);
+  if (!small && !mid) try_k_resident<TS>(p);
+  if (reuse && !p->have_v) {
+    set_error("gprhip: reuse_v set but this problem holds no V of a previous evaluation");
+    throw HipFail{ST_STATE};
   }
-  const int ksd = gemm_syrk_diag_slices(ks, !p->f32, true);  // the diagonal tiles (which also store the column sums) use fewer, longer slices
-  launch_reduce_rows(p->gemvpart, ksd, mp, ar1_c, 1, s);
-  tstop(p);
-  p->ks_used = ks;
-  launch_sum_slices<TS>(nullptr, slices, ks, mm, mp, ar1, s, 1, ksd);
+  p->have_v = false;
+  if (!reuse) p->have_k = p->small_k_valid = false;
+  const Ex1<double> ex = ex1_of(p, ar1);
+  const bool cov0_ahead = !reuse && !p->timer.on && !small && !mid;
+  if (cov0_ahead) fork_first_cov<TS>(p);
+  pass1_km_chol(p, ex, !(small || (mid && p->mp == TILE)) || reuse);
+  if (small && !reuse) pass1_small(p, ex);
+  else if (mid && !reuse) pass1_mid(p, ex);
+  else pass1_engine<TS>(p, ex, reuse, cov0_ahead);
   p->stage = 1;
   p->have_v = true;  // (revoked by finish() if the factorisation of K_m turns out to have failed)
-  if (!reuse) p->have_k = Kstore != nullptr && !rows_done;
+}
+
+// ---- pass 2
+// B~ = I + sum of shard parts; R~ = chol(B~): R = R~ U is the reference's r_mat (lib/fitc_gp.ml:181); R~^-1 and the m-vectors
+void pass2_b_chol(gprhip_problem* p, const Ex1<const double>& ex) {
+  hipStream_t s = p->stream;
+  const int mp = p->mp;
+  tstart(p, "b_chol");
+  const bool fused_b = mp == TILE && !p->engine_steps;
+  p->a1_in_scal = fused_b;
+  if (fused_b) {
+    // a single block: I + the accumulation, the factorisation, the inverse and the m-vectors below in one kernel
+    PotrfFuse f;
+    f.src = ex.tiles; f.cvec = ex.c;
+    f.tail_in = ex.tail; f.tail_out = p->scal + SC_A1TAIL;
+    f.uinv = p->uinv; f.bvec = p->bvec; f.ttil = p->ttil; f.tvec = p->tvec;
+    f.logdet = p->scal + SC_LOGDET_B; f.bb = p->scal + SC_BB;
+    launch_potrf_fused(f, p->bmat, p->rinv, p->info + 1, p->m, s);
+  } else {
+    hipLaunchKernelGGL(add_identity_upper_kernel, dim3((mp + 255) / 256, mp), dim3(256), 0, s, ex.tiles, mp,
+                       p->bmat);
+    potrf_trtri(p, p->bmat, p->rinv, p->wmat, p->info + 1);
+  }
+  if (p->f32) launch_to_float(p->rinv, p->rinv_f, (int64_t)mp * mp, s);
+  // b = R~^-T c~ (= Q_n^T y~, lib/fitc_gp.ml:285-286);  t~ = R~^-1 b;  t = U^-1 t~ (trsv, :291 / :1167)
+  if (!fused_b) {
+    // (log|B~| and |b|^2 ride on the first two launches: two launches less on the chain)
+    launch_triu_matvec_rider(p->rinv, mp, ex.c, p->bvec, 1, 1, p->bmat, mp, p->scal + SC_LOGDET_B, s);
+    launch_triu_matvec_rider(p->rinv, mp, p->bvec, p->ttil, 0, 2, p->bvec, mp, p->scal + SC_BB, s);
+    launch_triu_matvec(p->uinv, mp, p->ttil, p->tvec, 0, s);
+  }
+  tstop(p);
+}
+
+// the fields the one-kernel row passes of small.hip and mid.hip share
+template <typename Args>
+void fill_row_pass2(const gprhip_problem* p, Args& a) {
+  const bool proj = p->has_proj();
+  a.cp = p->cp; a.pts = p->pts(); a.Z = p->Z; a.rinv = p->rinv; a.bvec = p->bvec; a.ttil = p->ttil;
+  a.V = static_cast<const double*>(p->Vstore); a.y = p->h.model_only ? nullptr : p->y; a.is = p->is; a.r = p->r;
+  a.big = proj ? p->X : nullptr; a.D = proj ? p->D : 0;
+  a.rows = (int)p->n; a.rows_p = (int)round_up(p->n, TILE); a.m = p->m; a.mp = p->mp; a.d = p->d;
+  a.variational = p->h.variational;
+  // (X itself is only kept for the debug fetch "x_rows", which wants all rows in one chunk buffer)
+  a.w = p->w; a.v = p->v; a.es = proj ? p->es : nullptr; a.X = p->nchunks == 1 ? static_cast<double*>(p->bufB) : nullptr;
+}
+
+// at most 64 inducing points: Q', the row quantities, X~, X, the column sums of E = X .* K and G~ in one kernel (small.hip);
+// B~^-1 is formed by the finish kernel, R^-1 is not needed
+void pass2_small(gprhip_problem* p, const Ex2<double>& ex) {
+  tstart(p, "p2_small");
+  p->merged_x = false;
+  SmallPass2Args a;
+  fill_row_pass2(p, a);
+  a.uinv = p->uinv;
+  a.Kin = (p->small_k_valid && p->d <= 8 && !p->has_ms()) ? p->small_k : nullptr;
+  a.part = p->small_part;
+  launch_small_pass2(a, (int)p->col_rows(), ex.tiles, ex.col, ex.proj, ex.tail, p->stream);
+  p->x_last = a.X;
+  tstop(p);
+}
+
+// one or two 128-column tiles: Q', the row quantities, X~, X, E = X .* K with its moments (and, one tile, G~) in one
+// kernel (mid.hip); B~^-1 is formed by the finish kernels, R^-1 is not needed.  Two tiles: mid rows, then the Gram
+// accumulation G~_part = V^T diag(v) V -- by mid.hip's launch pair or by the engine's launch, as in pass 1
+void pass2_mid(gprhip_problem* p, const Ex2<double>& ex) {
+  hipStream_t s = p->stream;
+  tstart(p, "p2_mid");
+  p->merged_x = false;
+  // (U^-T and R~^-T for the "times B^T" products and the finish stage: W~'s and B~^-1's buffers are free on this path)
+  launch_mid_transposes(p->uinv, p->rinv, p->mp, p->wtil, p->binv, s);
+  MidPass2Args a;
+  fill_row_pass2(p, a);
+  a.uinvT = p->wtil; a.rinvT = p->binv; a.shift = p->zshift;
+  a.part = p->mid_part;
+  launch_mid_pass2(a, (int)p->col_rows(), ex.tiles, ex.col, ex.proj, ex.tail, s);
+  p->x_last = a.X;
+  if (p->has_proj()) {  // second term of the `Proj derivative from the per-row sums of E the kernel left (as the engine path)
+    for (int c = 0; c < p->nchunks; ++c) {
+      const int64_t rows = p->rows_of(c), base = (int64_t)c * p->chunk;
+      launch_proj_term2(p->X + base * p->D, p->P + base * p->d, p->es + base, 1, (int)rows, p->D, p->d, p->projpart, s);
+      launch_reduce_rows(p->projpart, (int)((rows + 255) / 256), p->D * p->d, ex.proj, 1, s);
+    }
+  }
+  tstop(p);
+  if (p->mp > TILE) gram_over_v<double>(p, 2, p->mid_pair(), ex.tiles, nullptr);
+}
+
+// the chunked engine path: the m x m inverses beside the first chunk, per row chunk Q', the row quantities, X and the
+// gradient accumulators, then one Gram accumulation over all rows
+template <typename TS>
+void pass2_engine(gprhip_problem* p, const Ex2<double>& ex) {
+  hipStream_t s = p->stream;
+  const int mp = p->mp;
+  const int64_t mm = (int64_t)mp * mp;
+  const bool mo = p->h.model_only != 0;
+  const bool proj = p->has_proj();
+  TS* const Vstore = static_cast<TS*>(p->Vstore);
+  TS* const bufA = static_cast<TS*>(p->bufA);
+  TS* const bufB = static_cast<TS*>(p->bufB);
+  // B~^-1 = R~^-1 R~^-T (needed by the finish stage only) and R^-1 = U^-1 R~^-1 (needed by the first X product) do not
+  // belong on the chain between the factorisation and the Q' products: they go to the second stream and run beside
+  // the first chunk's Q' launch (0.28 ms of every gradient evaluation at m = 2048).  Both use the split-K scratch,
+  // which the main stream touches next in the pass-2 SYRK -- it waits for ev_binv before that.  (Under the per-stage
+  // timer everything stays on the main stream, so that "inverses" keeps its meaning.)
+  const bool side = !p->timer.on;
+  hipStream_t si = side ? p->stream2 : s;
+  if (side) {
+    GPR_HIP(hipEventRecord(p->ev_fork, s));  // R~^-1 (and its fp32 copy), t~, t are enqueued on s
+    GPR_HIP(hipStreamWaitEvent(p->stream2, p->ev_fork, 0));
+  }
+  tstart(p, "inverses");
+  // The two-phase X product (below) needs R^-1 = U^-1 R~^-1, one more m x m product (0.14 ms at m = 2048, 0.8 ms at
+  // m = 4096), and saves 2.5 us per 1000 training points at m = 2048 (6 us at m = 4096): taken from 48 m training
+  // points per shard on.
+  p->merged_x = p->merged_x_mode == 2 || (p->merged_x_mode == 1 && p->n >= 48 * (int64_t)p->m);
+  if (p->merged_x) {
+    GemmArgs rf;  // R^-1 = U^-1 R~^-1, both upper triangular
+    rf.A = p->uinv; rf.lda = mp; rf.B = p->rinv; rf.ldb = mp; rf.C = p->rfinv; rf.ldc = mp;
+    rf.M = mp; rf.N = mp; rf.K = mp; rf.tri = TRI_BAND; rf.upper_only = 1;
+    // the corner tile's k-range is the whole of m: eight k-slices keep the launch from waiting on it
+    const int rks = (mp >= 1024 && 8 * mm * 8 <= p->slices_bytes) ? 8 : 1;
+    if (rks > 1) {
+      rf.C = static_cast<double*>(p->slices);
+      rf.kslices = rks;
+      rf.slice_stride = mm;
+      launch_gemm(OP_NN, rf, si);
+      launch_sum_slices<double>(nullptr, static_cast<double*>(p->slices), rks, mm, mp, p->rfinv, si);
+    } else {
+      launch_gemm(OP_NN, rf, si);
+    }
+    if (p->f32) launch_to_float(p->rfinv, p->rfinv_f, mm, si);
+  }
+  if (side) GPR_HIP(hipEventRecord(p->ev_rf, si));
+  triu_xxt(p, p->rinv, p->binv, si);  // B~^-1 (upper tiles)
+  if (side) GPR_HIP(hipEventRecord(p->ev_binv, si));
+  tstop(p);
+  bool derive_inducing = false;
+  for (int c = 0; c < p->nchunks; ++c) {
+    const int64_t rows = p->rows_of(c);
+    const int rows_p = (int)round_up(rows, TILE);
+    const int64_t base = (int64_t)c * p->chunk;
+    const TS* V = Vstore + base * mp;
+    tstart(p, "p2_trmm_Q");
+    GemmArgsT<TS> q;  // Q' = V R~^-1 = K R^-1  (Q_n = diag(sqrt is) Q', lib/fitc_gp.ml:176-182)
+    q.A = V; q.lda = mp; q.B = inv_r<TS>(p); q.ldb = mp; q.C = bufA; q.ldc = mp;
+    q.M = rows_p; q.N = mp; q.K = mp; q.tri = TRI_KHI_BN; q.order = p->tile_order;
+    q.rp_sumsq = p->rp1; q.rp_dot = p->rp2; q.rp_vec = p->bvec;  // q_diag and Q'b from the epilogue
+    launch_gemm(OP_NN, q, s);
+    tstop(p);
+    tstart(p, "p2_rows");
+    Pass2RowArgs ra;
+    ra.part_sq = p->rp1; ra.part_dot = p->rp2; ra.npart = gemm_row_parts_per_tile() * (mp / TILE); ra.ld = rows_p;
+    ra.y = mo ? nullptr : p->y + base; ra.is = p->is + base; ra.r = p->r + base;
+    ra.rows = (int)rows; ra.variational = p->h.variational;
+    ra.sf2 = p->cp.sf2; ra.es = proj ? p->es + base : nullptr;
+    ra.w = p->w + base; ra.v = p->v + base; ra.partial = p->rowpart;
+    launch_pass2_rows(ra, s);
+    launch_reduce_rows(p->rowpart, pass1_row_blocks(rows_p), 4, ex.tail, 1, s);
+    tstop(p);
+    if constexpr (std::is_same<TS, double>::value)
+      if (p->multi) targets_pass2_rows(p, bufA, base, (int)rows, proj ? p->es + base : nullptr, ex.tail + A2_SUMV);
+    const TS* Xc;  // X of this chunk
+    if (p->merged_x) {
+      // X = diag(is) Q' R^-T - diag(v) V U^-T - w t^T  (S, U_mat and the ger of lib/fitc_gp.ml:931-939, :1204-1206) as
+      // one launch of two-phase items: acc = V U^-T, rows scaled by -v/is, acc += Q' R^-T, epilogue is*acc - w t^T --
+      // one epilogue per tile instead of two, no X~ round trip, no operand read in the epilogue
+      if (side && c == 0) GPR_HIP(hipStreamWaitEvent(s, p->ev_rf, 0));
+      tstart(p, "p2_trmm_SX");
+      GemmArgsT<TS> xg;
+      xg.A = bufA; xg.lda = mp; xg.B = inv_rfull<TS>(p); xg.ldb = mp; xg.C = bufB; xg.ldc = mp;
+      xg.A2 = V; xg.B2 = inv_u<TS>(p); xg.mid_num = p->v + base; xg.mid_den = p->is + base;
+      xg.M = rows_p; xg.N = mp; xg.K = mp; xg.tri = TRI_KLO_BN; xg.order = p->tile_order;
+      xg.epi_rows_a = p->is + base; xg.epi_rows_c = p->w + base; xg.epi_col = p->tvec;
+      launch_gemm(OP_NT, xg, s);
+      tstop(p);
+      Xc = bufB;
+    } else {
+      tstart(p, "p2_trmm_S");
+      GemmArgsT<TS> sg;  // X~ = diag(is) Q' R~^-T - diag(v) V - w t~^T   (S, U_mat and the ger of :936-938, :1204-1206)
+      sg.A = bufA; sg.lda = mp; sg.B = inv_r<TS>(p); sg.ldb = mp; sg.C = bufB; sg.ldc = mp;
+      sg.M = rows_p; sg.N = mp; sg.K = mp; sg.tri = TRI_KLO_BN; sg.order = p->tile_order;
+      sg.epi_rows_a = p->is + base; sg.epi_rows_b = p->v + base; sg.epi_rows_c = p->w + base;
+      sg.epi_col = p->ttil; sg.epi_mat = V; sg.epi_ldm = mp;
+      launch_gemm(OP_NT, sg, s);
+      tstop(p);
+      tstart(p, "p2_trmm_X");
+      GemmArgsT<TS> xg;  // X = X~ U^-T
+      xg.A = bufB; xg.lda = mp; xg.B = inv_u<TS>(p); xg.ldb = mp; xg.C = bufA; xg.ldc = mp;
+      xg.M = rows_p; xg.N = mp; xg.K = mp; xg.tri = TRI_KLO_BN; xg.order = p->tile_order;
+      launch_gemm(OP_NT, xg, s);
+      tstop(p);
+      Xc = bufA;
+    }
+    p->x_last = (p->nchunks == 1) ? static_cast<const void*>(Xc) : nullptr;
+    if constexpr (std::is_same<TS, double>::value)
+      if (p->multi) targets_xcorr(p, const_cast<double*>(Xc), base, (int)rows);
+    tstart(p, "p2_grad");
+    GradArgs<TS> ga;
+    ga.X = Xc; ga.pts = p->pts() + base * p->d; ga.Z = p->Z;
+    ga.rows = (int)rows; ga.rows_p = rows_p; ga.m = p->m; ga.mp = mp; ga.d = p->d;
+    ga.log_sf2 = p->cp.log_sf2; ga.inv_ell2_05 = p->cp.inv_ell2_05;
+    ga.colpart = p->colpart; ga.scalpart = p->scalpart;
+    ga.big = proj ? p->X + base * p->D : nullptr; ga.D = proj ? p->D : 0;
+    ga.ms = p->cp.ms; ga.shift = p->zshift;
+    ga.K = (p->Kstore && p->have_k && proj && !ga.ms) ? static_cast<const TS*>(p->Kstore) + base * mp : nullptr;
+    ga.col_rows = p->d + 1 + ga.D + (ga.ms ? p->d : 0);  // rows this launch produces (tightly packed)
+    ga.slab = p->grad_slab;
+    const int nslots = 4 * ((mp + 255) / 256);
+    ga.rowes = (ga.ms && proj) ? p->rowes : nullptr;
+    // matrix-core version unless multiscales (or > 64 dimensions) need the scalar kernel; GPRHIP_GRAD_SCALAR=1
+    // forces the scalar one (parity tests run both)
+    int nbx = p->grad_scalar ? 0 : grad_mfma_col_blocks(ga);
+    if (p->d > 64 || ga.D > 64) {
+      // wide points: K of the chunk is rebuilt into the chunk buffer that does not hold X, and E = X .* K read from memory
+      TS* const Kw = (Xc == bufA) ? bufB : bufA;
+      cov_chunk<TS>(p, c, Kw);
+      launch_grad_wide(ga, static_cast<const TS*>(Kw), s);
+      nbx = (mp + 255) / 256;
+    } else if (nbx > 0) {
+      launch_grad_mfma(ga, s);
+      derive_inducing = proj;  // that kernel accumulates only the projection-gradient sums (grad_mfma.hip)
+    } else {
+      launch_grad_fused(ga, s);
+      nbx = (mp + 255) / 256;
+    }
+    const int nslabs = (int)((rows + ga.slab - 1) / ga.slab);
+    launch_reduce_rows(p->colpart, nslabs, ga.col_rows * mp, ex.col, 1, s);
+    if (proj) {
+      if (ga.ms) {
+        launch_reduce_rowes(p->rowes, (int)rows, nslots, p->d, p->es2, s);
+        launch_proj_term2(p->X + base * p->D, p->P + base * p->d, p->es2, p->d, (int)rows, p->D, p->d,
+                          p->projpart, s);
+      } else {
+        launch_proj_term2(p->X + base * p->D, p->P + base * p->d, p->es + base, 1, (int)rows, p->D, p->d,
+                          p->projpart, s);
+      }
+      launch_reduce_rows(p->projpart, (int)((rows + 255) / 256), p->D * p->d, ex.proj, 1, s);
+    }
+    launch_reduce_rows(p->scalpart, nslabs * nbx, 2, ex.tail + A2_SUME, 1, s);
+    tstop(p);
+  }
+  if (derive_inducing) launch_proj_inducing_grad(ex.col, mp, p->d, p->D, p->tproj, s);
+  if (side) GPR_HIP(hipStreamWaitEvent(s, p->ev_binv, 0));  // B~^-1 done: the split-K scratch is free again
+  gram_over_v<TS>(p, 2, false, ex.tiles, nullptr);
 }
 
 template <typename TS>
@@ -1001,380 +1318,82 @@ void do_pass2(gprhip_problem* p, const double* ar1, double* ar2) {
     throw HipFail{ST_STATE};
   }
   GPR_HIP(hipSetDevice(p->device));
-  hipStream_t s = p->stream;
-  const int mp = p->mp;
-  const int64_t mm = (int64_t)mp * mp;
-  const double* ar1_c = ar1 + packed_upper_len(mp);
-  double* ar2_col = ar2 + packed_upper_len(mp);
-  double* ar2_proj = ar2_col + p->col_rows() * mp;
-  double* ar2_tail = ar2_proj + (int64_t)p->dbig() * p->d;
-  const bool mo = p->h.model_only != 0;
-  const bool proj = p->has_proj();
-
-  tstart(p, "b_chol");
-  // B~ = I + sum of shard parts; R~ = chol(B~): R = R~ U is the reference's r_mat (lib/fitc_gp.ml:181)
-  const bool fused_b = mp == TILE && !p->engine_steps;
-  p->a1_in_scal = fused_b;
-  if (fused_b) {
-    // a single block: I + the accumulation, the factorisation, the inverse and the m-vectors below in one kernel
-    PotrfFuse f;
-    f.src = ar1; f.cvec = ar1_c;
-    f.tail_in = ar1_c + mp; f.tail_out = p->scal + SC_A1TAIL;
-    f.uinv = p->uinv; f.bvec = p->bvec; f.ttil = p->ttil; f.tvec = p->tvec;
-    f.logdet = p->scal + SC_LOGDET_B; f.bb = p->scal + SC_BB;
-    launch_potrf_fused(f, p->bmat, p->rinv, p->info + 1, p->m, s);
-  } else {
-    hipLaunchKernelGGL(add_identity_upper_kernel, dim3((mp + 255) / 256, mp), dim3(256), 0, s, ar1, mp,
-                       p->bmat);
-    potrf_trtri(p, p->bmat, p->rinv, p->wmat, p->info + 1);
-  }
-  if (p->f32) launch_to_float(p->rinv, p->rinv_f, mm, s);
-  TS* const Vstore = static_cast<TS*>(p->Vstore);
-  TS* const bufA = static_cast<TS*>(p->bufA);
-  TS* const bufB = static_cast<TS*>(p->bufB);
-  TS* const slices = static_cast<TS*>(p->slices);
-  // b = R~^-T c~ (= Q_n^T y~, lib/fitc_gp.ml:285-286);  t~ = R~^-1 b;  t = U^-1 t~ (trsv, :291 / :1167)
-  if (!fused_b) {
-    // (log|B~| and |b|^2 ride on the first two launches: two launches less on the chain)
-    launch_triu_matvec_rider(p->rinv, mp, ar1_c, p->bvec, 1, 1, p->bmat, mp, p->scal + SC_LOGDET_B, s);
-    launch_triu_matvec_rider(p->rinv, mp, p->bvec, p->ttil, 0, 2, p->bvec, mp, p->scal + SC_BB, s);
-    launch_triu_matvec(p->uinv, mp, p->ttil, p->tvec, 0, s);
-  }
-  tstop(p);
-  if constexpr (std::is_same<TS, double>::value)
-    if (p->multi) targets_middle(p);  // (c~, b, t~, t above are those of no target: zero)
-
+  pass2_b_chol(p, ex1_of(p, ar1));
+  if (p->multi) targets_middle(p);  // (c~, b, t~, t above are those of no target: zero)
+  const Ex2<double> ex = ex2_of(p, ar2);
+  const bool small = p->use_small(), mid = p->use_mid();
   // evidence-only evaluations (multim_f) carry nothing in the second exchange buffer: only its scalar tail is cleared,
-  // and the caller need not reduce it
-  const bool small = p->use_small();  // its reduction writes every entry of the exchange-2 buffer
-  const bool mid = p->use_mid();      // (the same)
-  // (two tiles through mid.hip: its reduction writes everything behind the packed tiles, the engine's slice sum the tiles)
-  if (p->want_grad && !small && !mid) GPR_HIP(hipMemsetAsync(ar2, 0, (size_t)gprhip_ar2_len(p) * sizeof(double), s));
-  else if (!p->want_grad) GPR_HIP(hipMemsetAsync(ar2_tail, 0, (size_t)A2_TAIL * sizeof(double), s));
-  if constexpr (std::is_same<TS, double>::value) {
-    if (p->want_grad && small) {
-      // at most 64 inducing points: Q', the row quantities, X~, X, the column sums of E = X .* K and G~ in one kernel (small.hip);
-      // B~^-1 is formed by the finish kernel, R^-1 is not needed
-      tstart(p, "p2_small");
-      if (!p->small_part) p->small_part = p->alloc<double>(small_part_len(p->d, p->D));
-      p->merged_x = false;
-      SmallPass2Args a;
-      a.cp = p->cp; a.pts = p->pts(); a.Z = p->Z; a.uinv = p->uinv; a.rinv = p->rinv; a.bvec = p->bvec; a.ttil = p->ttil;
-      a.V = Vstore; a.y = mo ? nullptr : p->y; a.is = p->is; a.r = p->r;
-      a.Kin = (p->small_k_valid && p->d <= 8 && !p->has_ms()) ? p->small_k : nullptr;
-      a.big = proj ? p->X : nullptr; a.D = proj ? p->D : 0;
-      a.rows = (int)p->n; a.rows_p = (int)round_up(p->n, TILE); a.m = p->m; a.mp = mp; a.d = p->d;
-      a.variational = p->h.variational;
-      // (X itself is only kept for the debug fetch "x_rows", which wants all rows in one chunk buffer)
-      a.w = p->w; a.v = p->v; a.es = proj ? p->es : nullptr; a.X = p->nchunks == 1 ? bufB : nullptr; a.part = p->small_part;
-      launch_small_pass2(a, (int)p->col_rows(), ar2, ar2_col, ar2_proj, ar2_tail, s);
-      p->x_last = a.X;
-      tstop(p);
-      p->stage = 2;
-      return;
-    }
-    if (p->want_grad && mid) {
-      // one or two 128-column tiles: Q', the row quantities, X~, X, E = X .* K with its moments (and, one tile, G~) in one
-      // kernel (mid.hip); B~^-1 is formed by the finish kernels, R^-1 is not needed
-      tstart(p, "p2_mid");
-      if (!p->mid_part) p->mid_part = p->alloc<double>(mid_part_len(mp, p->d, p->D));
-      p->merged_x = false;
-      // (U^-T and R~^-T for the "times B^T" products and the finish stage: W~'s and B~^-1's buffers are free on this path)
-      launch_mid_transposes(p->uinv, p->rinv, mp, p->wtil, p->binv, s);
-      MidPass2Args a;
-      a.cp = p->cp; a.pts = p->pts(); a.Z = p->Z; a.rinv = p->rinv; a.uinvT = p->wtil; a.rinvT = p->binv;
-      a.bvec = p->bvec; a.ttil = p->ttil;
-      a.V = Vstore; a.y = mo ? nullptr : p->y; a.is = p->is; a.r = p->r;
-      a.big = proj ? p->X : nullptr; a.D = proj ? p->D : 0; a.shift = p->zshift;
-      a.rows = (int)p->n; a.rows_p = (int)round_up(p->n, TILE); a.m = p->m; a.mp = mp; a.d = p->d;
-      a.variational = p->h.variational;
-      a.w = p->w; a.v = p->v; a.es = proj ? p->es : nullptr; a.X = p->nchunks == 1 ? bufB : nullptr; a.part = p->mid_part;
-      launch_mid_pass2(a, (int)p->col_rows(), ar2, ar2_col, ar2_proj, ar2_tail, s);
-      p->x_last = a.X;
-      if (proj) {  // second term of the `Proj derivative from the per-row sums of E the kernel left (as the engine path)
-        for (int c = 0; c < p->nchunks; ++c) {
-          const int64_t rows = p->rows_of(c), base = (int64_t)c * p->chunk;
-          launch_proj_term2(p->X + base * p->D, p->P + base * p->d, p->es + base, 1, (int)rows, p->D, p->d, p->projpart, s);
-          launch_reduce_rows(p->projpart, (int)((rows + 255) / 256), p->D * p->d, ar2_proj, 1, s);
-        }
-      }
-      tstop(p);
-      if (mp > TILE && p->use_mid_gram()) {  // two tiles: G~_part = V^T diag(v) V by the Gram launch pair of mid.hip
-        tstart(p, "p2_syrk_W");
-        if (!p->mid_gram_part) p->mid_gram_part = p->alloc<double>(mid_gram_part_len());
-        MidGramArgs ga;
-        ga.V = reinterpret_cast<const double*>(Vstore); ga.w = p->v; ga.y = nullptr; ga.rows = (int)p->n;
-        ga.part = p->mid_gram_part;
-        launch_mid_gram(ga, ar2, nullptr, s);
-        tstop(p);
-      } else if (mp > TILE) {  // ... or from the engine, as below (GPRHIP_MID_GRAM=0)
-        tstart(p, "p2_syrk_W");
-        GemmArgsT<TS> wg;
-        wg.A = Vstore; wg.lda = mp; wg.B = Vstore; wg.ldb = mp; wg.C = slices; wg.ldc = mp;
-        wg.M = mp; wg.N = mp; wg.K = (int)p->rows_total_padded(); wg.beta = 0.0;
-        wg.scale_k = row_weights<TS>(p, p->v, p->v_f); wg.upper_only = 1;
-        wg.kslices = p->ks_used; wg.slice_stride = mm;
-        const bool as_ws = p->w_as_ws != 0;
-        if (as_ws) {
-          wg.cs_w = wg.scale_k;
-          wg.cs_out = p->gemvpart;
-        }
-        launch_gemm(OP_TN, wg, s);
-        tstop(p);
-        launch_sum_slices<TS>(nullptr, slices, p->ks_used, mm, mp, ar2, s, 1, gemm_syrk_diag_slices(p->ks_used, !p->f32, as_ws));
-      }
-      p->stage = 2;
-      return;
-    }
-  }
-  if (p->want_grad) {
-    // B~^-1 = R~^-1 R~^-T (needed by the finish stage only) and R^-1 = U^-1 R~^-1 (needed by the first X product) do not
-    // belong on the chain between the factorisation and the Q' products: they go to the second stream and run beside
-    // the first chunk's Q' launch (0.28 ms of every gradient evaluation at m = 2048).  Both use the split-K scratch,
-    // which the main stream touches next in the pass-2 SYRK -- it waits for ev_binv before that.  (Under the per-stage
-    // timer everything stays on the main stream, so that "inverses" keeps its meaning.)
-    const bool side = !p->timer.on;
-    hipStream_t si = side ? p->stream2 : s;
-    if (side) {
-      GPR_HIP(hipEventRecord(p->ev_fork, s));  // R~^-1 (and its fp32 copy), t~, t are enqueued on s
-      GPR_HIP(hipStreamWaitEvent(p->stream2, p->ev_fork, 0));
-    }
-    tstart(p, "inverses");
-    // The two-phase X product (below) needs R^-1 = U^-1 R~^-1, one more m x m product (0.14 ms at m = 2048, 0.8 ms at
-    // m = 4096), and saves 2.5 us per 1000 training points at m = 2048 (6 us at m = 4096): taken from 48 m training
-    // points per shard on.
-    p->merged_x = p->merged_x_mode == 2 || (p->merged_x_mode == 1 && p->n >= 48 * (int64_t)p->m);
-    if (p->merged_x) {
-      GemmArgs rf;  // R^-1 = U^-1 R~^-1, both upper triangular
-      rf.A = p->uinv; rf.lda = mp; rf.B = p->rinv; rf.ldb = mp; rf.C = p->rfinv; rf.ldc = mp;
-      rf.M = mp; rf.N = mp; rf.K = mp; rf.tri = TRI_BAND; rf.upper_only = 1;
-      // the corner tile's k-range is the whole of m: eight k-slices keep the launch from waiting on it
-      const int rks = (mp >= 1024 && 8 * mm * 8 <= p->slices_bytes) ? 8 : 1;
-      if (rks > 1) {
-        rf.C = static_cast<double*>(p->slices);
-        rf.kslices = rks;
-        rf.slice_stride = mm;
-        launch_gemm(OP_NN, rf, si);
-        launch_sum_slices<double>(nullptr, static_cast<double*>(p->slices), rks, mm, mp, p->rfinv, si);
-      } else {
-        launch_gemm(OP_NN, rf, si);
-      }
-      if (p->f32) launch_to_float(p->rfinv, p->rfinv_f, mm, si);
-    }
-    if (side) GPR_HIP(hipEventRecord(p->ev_rf, si));
-    triu_xxt(p, p->rinv, p->binv, si);  // B~^-1 (upper tiles)
-    if (side) GPR_HIP(hipEventRecord(p->ev_binv, si));
-    tstop(p);
-    bool derive_inducing = false;
-    for (int c = 0; c < p->nchunks; ++c) {
-      const int64_t rows = p->rows_of(c);
-      const int rows_p = (int)round_up(rows, TILE);
-      const int64_t base = (int64_t)c * p->chunk;
-      const TS* V = Vstore + base * mp;
-      tstart(p, "p2_trmm_Q");
-      GemmArgsT<TS> q;  // Q' = V R~^-1 = K R^-1  (Q_n = diag(sqrt is) Q', lib/fitc_gp.ml:176-182)
-      q.A = V; q.lda = mp; q.B = inv_r<TS>(p); q.ldb = mp; q.C = bufA; q.ldc = mp;
-      q.M = rows_p; q.N = mp; q.K = mp; q.tri = TRI_KHI_BN; q.order = p->tile_order;
-      q.rp_sumsq = p->rp1; q.rp_dot = p->rp2; q.rp_vec = p->bvec;  // q_diag and Q'b from the epilogue
-      launch_gemm(OP_NN, q, s);
-      tstop(p);
-      tstart(p, "p2_rows");
-      Pass2RowArgs ra;
-      ra.part_sq = p->rp1; ra.part_dot = p->rp2; ra.npart = gemm_row_parts_per_tile() * (mp / TILE); ra.ld = rows_p;
-      ra.y = mo ? nullptr : p->y + base; ra.is = p->is + base; ra.r = p->r + base;
-      ra.rows = (int)rows; ra.variational = p->h.variational;
-      ra.sf2 = p->cp.sf2; ra.es = proj ? p->es + base : nullptr;
-      ra.w = p->w + base; ra.v = p->v + base; ra.partial = p->rowpart;
-      launch_pass2_rows(ra, s);
-      launch_reduce_rows(p->rowpart, pass1_row_blocks(rows_p), 4, ar2_tail, 1, s);
-      tstop(p);
-      if constexpr (std::is_same<TS, double>::value)
-        if (p->multi) targets_pass2_rows(p, bufA, base, (int)rows, proj ? p->es + base : nullptr, ar2_tail + A2_SUMV);
-      const TS* Xc;  // X of this chunk
-      if (p->merged_x) {
-        // X = diag(is) Q' R^-T - diag(v) V U^-T - w t^T  (S, U_mat and the ger of lib/fitc_gp.ml:931-939, :1204-1206) as
-        // one launch of two-phase items: acc = V U^-T, rows scaled by -v/is, acc += Q' R^-T, epilogue is*acc - w t^T --
-        // one epilogue per tile instead of two, no X~ round trip, no operand read in the epilogue
-        if (side && c == 0) GPR_HIP(hipStreamWaitEvent(s, p->ev_rf, 0));
-        tstart(p, "p2_trmm_SX");
-        GemmArgsT<TS> xg;
-        xg.A = bufA; xg.lda = mp; xg.B = inv_rfull<TS>(p); xg.ldb = mp; xg.C = bufB; xg.ldc = mp;
-        xg.A2 = V; xg.B2 = inv_u<TS>(p); xg.mid_num = p->v + base; xg.mid_den = p->is + base;
-        xg.M = rows_p; xg.N = mp; xg.K = mp; xg.tri = TRI_KLO_BN; xg.order = p->tile_order;
-        xg.epi_rows_a = p->is + base; xg.epi_rows_c = p->w + base; xg.epi_col = p->tvec;
-        launch_gemm(OP_NT, xg, s);
-        tstop(p);
-        Xc = bufB;
-      } else {
-        tstart(p, "p2_trmm_S");
-        GemmArgsT<TS> sg;  // X~ = diag(is) Q' R~^-T - diag(v) V - w t~^T   (S, U_mat and the ger of :936-938, :1204-1206)
-        sg.A = bufA; sg.lda = mp; sg.B = inv_r<TS>(p); sg.ldb = mp; sg.C = bufB; sg.ldc = mp;
-        sg.M = rows_p; sg.N = mp; sg.K = mp; sg.tri = TRI_KLO_BN; sg.order = p->tile_order;
-        sg.epi_rows_a = p->is + base; sg.epi_rows_b = p->v + base; sg.epi_rows_c = p->w + base;
-        sg.epi_col = p->ttil; sg.epi_mat = V; sg.epi_ldm = mp;
-        launch_gemm(OP_NT, sg, s);
-        tstop(p);
-        tstart(p, "p2_trmm_X");
-        GemmArgsT<TS> xg;  // X = X~ U^-T
-        xg.A = bufB; xg.lda = mp; xg.B = inv_u<TS>(p); xg.ldb = mp; xg.C = bufA; xg.ldc = mp;
-        xg.M = rows_p; xg.N = mp; xg.K = mp; xg.tri = TRI_KLO_BN; xg.order = p->tile_order;
-        launch_gemm(OP_NT, xg, s);
-        tstop(p);
-        Xc = bufA;
-      }
-      p->x_last = (p->nchunks == 1) ? static_cast<const void*>(Xc) : nullptr;
-      if constexpr (std::is_same<TS, double>::value)
-        if (p->multi) targets_xcorr(p, const_cast<double*>(Xc), base, (int)rows);
-      tstart(p, "p2_grad");
-      GradArgs<TS> ga;
-      ga.X = Xc; ga.pts = p->pts() + base * p->d; ga.Z = p->Z;
-      ga.rows = (int)rows; ga.rows_p = rows_p; ga.m = p->m; ga.mp = mp; ga.d = p->d;
-      ga.log_sf2 = p->cp.log_sf2; ga.inv_ell2_05 = p->cp.inv_ell2_05;
-      ga.colpart = p->colpart; ga.scalpart = p->scalpart;
-      ga.big = proj ? p->X + base * p->D : nullptr; ga.D = proj ? p->D : 0;
-      ga.ms = p->cp.ms; ga.rowes = nullptr; ga.shift = p->zshift;
-      ga.K = (p->Kstore && p->have_k && proj && !ga.ms) ? static_cast<const TS*>(p->Kstore) + base * mp : nullptr;
-      ga.col_rows = p->d + 1 + ga.D + (ga.ms ? p->d : 0);  // rows this launch produces (tightly packed)
-      ga.slab = p->grad_slab;
-      const int nslots = 4 * ((mp + 255) / 256);
-      if (ga.ms && proj) {
-        if (!p->rowes) {
-          p->rowes = p->alloc<double>(p->chunk * nslots * p->d);
-          p->es2 = p->alloc<double>(p->chunk * p->d);
-        }
-        ga.rowes = p->rowes;
-      }
-      // matrix-core version unless multiscales (or > 64 dimensions) need the scalar kernel; GPRHIP_GRAD_SCALAR=1
-      // forces the scalar one (parity tests run both)
-      int nbx = p->grad_scalar ? 0 : grad_mfma_col_blocks(ga);
-      if (p->d > 64 || ga.D > 64) {
-        // wide points: K of the chunk is rebuilt into the chunk buffer that does not hold X, and E = X .* K read from memory
-        TS* const Kw = (Xc == bufA) ? bufB : bufA;
-        cov_chunk<TS>(p, c, Kw);
-        launch_grad_wide(ga, static_cast<const TS*>(Kw), s);
-        nbx = (mp + 255) / 256;
-      } else if (nbx > 0) {
-        launch_grad_mfma(ga, s);
-        derive_inducing = proj;  // that kernel accumulates only the projection-gradient sums (grad_mfma.hip)
-      } else {
-        launch_grad_fused(ga, s);
-        nbx = (mp + 255) / 256;
-      }
-      const int nslabs = (int)((rows + ga.slab - 1) / ga.slab);
-      launch_reduce_rows(p->colpart, nslabs, ga.col_rows * mp, ar2_col, 1, s);
-      if (proj) {
-        if (ga.ms) {
-          launch_reduce_rowes(p->rowes, (int)rows, nslots, p->d, p->es2, s);
-          launch_proj_term2(p->X + base * p->D, p->P + base * p->d, p->es2, p->d, (int)rows, p->D, p->d,
-                            p->projpart, s);
-        } else {
-          launch_proj_term2(p->X + base * p->D, p->P + base * p->d, p->es + base, 1, (int)rows, p->D, p->d,
-                            p->projpart, s);
-        }
-        launch_reduce_rows(p->projpart, (int)((rows + 255) / 256), p->D * p->d, ar2_proj, 1, s);
-      }
-      launch_reduce_rows(p->scalpart, nslabs * nbx, 2, ar2_tail + A2_SUME, 1, s);
-      tstop(p);
-    }
-    if (derive_inducing) launch_proj_inducing_grad(ar2_col, mp, p->d, p->D, p->tproj, s);
-    // G~_part = V^T diag(v) V over all rows (the two dsyrk of lib/fitc_gp.ml:1198-1203, whitened, in one)
-    const int64_t ktot = p->rows_total_padded();
-    if (side) GPR_HIP(hipStreamWaitEvent(s, p->ev_binv, 0));  // B~^-1 done: the split-K scratch is free again
-    tstart(p, "p2_syrk_W");
-    GemmArgsT<TS> wg;
-    wg.A = Vstore; wg.lda = mp; wg.B = Vstore; wg.ldb = mp; wg.C = slices; wg.ldc = mp;
-    wg.M = mp; wg.N = mp; wg.K = (int)ktot; wg.beta = 0.0; wg.scale_k = row_weights<TS>(p, p->v, p->v_f); wg.upper_only = 1;
-    wg.kslices = p->ks_used; wg.slice_stride = mm;
-    // The pass-2 launch goes through the kernel of the pass-1 one (its diagonal tiles then also form column sums nobody
-    // reads): measured in round 4, the plain weighted kernel (gemm_*_tn_w) runs this very launch with 172 GB instead of
-    // 67 GB through the fabric and 1-2 ms slower on most boxes of the pool -- its workgroups fall out of step from the
-    // first residency round on -- while the column-sum kernel does not (tools/lab19.sh, lab20.sh; GPRHIP_W_AS_WS=0 restores
-    // the plain kernel).
-    const bool as_ws = p->w_as_ws != 0;
-    if (as_ws) {
-      wg.cs_w = wg.scale_k;
-      wg.cs_out = p->gemvpart;
-    }
-    launch_gemm(OP_TN, wg, s);
-    tstop(p);
-    launch_sum_slices<TS>(nullptr, slices, p->ks_used, mm, mp, ar2, s, 1, gemm_syrk_diag_slices(p->ks_used, !p->f32, as_ws));
+  // and the caller need not reduce it.  The reductions of the small and the mid pass write every entry of the buffer
+  // (two tiles through mid.hip: its reduction writes everything behind the packed tiles, the Gram accumulation the tiles)
+  if (!p->want_grad) GPR_HIP(hipMemsetAsync(ex.tail, 0, (size_t)A2_TAIL * sizeof(double), p->stream));
+  else if (small) pass2_small(p, ex);
+  else if (mid) pass2_mid(p, ex);
+  else {
+    GPR_HIP(hipMemsetAsync(ar2, 0, (size_t)gprhip_ar2_len(p) * sizeof(double), p->stream));
+    pass2_engine<TS>(p, ex);
   }
   p->stage = 2;
 }
 
-// Finish stage, first half: the m x m work of the gradient (W, traces) and the asynchronous copies of everything the
-// host assembly needs, all on the problem's stream; nothing blocks.  `light` (shards of a multi-device context other
-// than the first): only the factorisation flags are fetched -- the reduced buffers are identical on every device, and
-// one device's assembly serves the caller.
-void do_finish_enqueue(gprhip_problem* p, const double* ar2, bool light = false) {
-  if (p->stage != 2) {
-    set_error("gprhip: eval_finish called before eval_pass2");
-    throw HipFail{ST_STATE};
+// ---- finish stage, first half, per path
+bool wants_wdiag(const gprhip_problem* p) { return p->want_grad && (p->has_het() || p->has_ms()); }
+
+// at most 64 inducing points: the m x m work in one workgroup, which also gathers the exchange-2 tail behind the
+// result block
+void finish_small(gprhip_problem* p, const Ex2<const double>& ex) {
+  hipStream_t s = p->stream;
+  const int d = p->d;
+  tstart(p, "finish");
+  SmallFinishArgs a;
+  a.uinv = p->uinv; a.rinv = p->rinv; a.ttil = p->ttil; a.km = p->km; a.Z = p->Z; a.g = ex.tiles;
+  a.ms = p->has_ms() ? p->ms : nullptr;
+  a.m = p->m; a.mp = p->mp; a.d = d; a.km_rows = p->has_ms() ? 2 * d + 2 : d + 2;
+  a.wmat = p->wmat; a.kmred = p->kmred; a.wdiag = wants_wdiag(p) ? p->wdiag : nullptr;
+  a.gather_from = ex.col; a.n_gather = ex.len_from_col(); a.ex = p->ex_dev + A1_TAIL;
+  launch_small_finish(a, s);
+  tstop(p);
+  const int64_t n_res = p->res_len + A1_TAIL + ex.len_from_col();
+  if (n_res * (int64_t)sizeof(double) > 32768) {  // (d > 8 or so: above 32 KB a copy starts 17 us late, a kernel at once)
+    ShipArgs sh;
+    sh.src[0] = p->res_dev; sh.dst[0] = p->res_host; sh.n[0] = n_res;
+    launch_ship(sh, s);
+  } else {
+    GPR_HIP(hipMemcpyAsync(p->res_host, p->res_dev, (size_t)n_res * sizeof(double), hipMemcpyDeviceToHost, s));
   }
-  GPR_HIP(hipSetDevice(p->device));
+}
+
+// one or two 128-blocks: the m x m work in two launches of one workgroup per 16 rows (mid.hip), the first of which also
+// gathers the exchange-2 tail behind the result block
+void finish_mid(gprhip_problem* p, const Ex2<const double>& ex) {
+  tstart(p, "finish");
+  MidFinishArgs a;
+  a.uinv = p->uinv; a.rinv = p->rinv; a.uinvT = p->wtil; a.rinvT = p->binv; a.ttil = p->ttil; a.km = p->km; a.Z = p->Z;
+  a.g = ex.tiles;
+  a.m = p->m; a.mp = p->mp; a.d = p->d; a.km_rows = p->d + 2;
+  a.wmat = p->wmat; a.kmred = p->kmred; a.wdiag = wants_wdiag(p) ? p->wdiag : nullptr;
+  a.ybuf = p->kj;  // (free after the factorisation of K_m)
+  a.gather_from = ex.col; a.n_gather = ex.len_from_col(); a.ex = p->ex_dev + A1_TAIL;
+  // the kernels' last workgroup writes the result block (and, two tiles, the exchange-1 tail) into the pinned mirror itself
+  a.res_dev = p->res_dev; a.res_host = p->res_host; a.res_total = p->res_len + A1_TAIL + ex.len_from_col();
+  a.done_ctr = p->mid_done;
+  if (!p->a1_in_scal) {  // (two tiles: the B~ phase is not the fused single-block kernel that leaves the tail in the result block)
+    a.a1_tail = ex1_of(p, p->ar1).tail;
+    a.a1_host = p->ex_host;
+  }
+  launch_mid_finish(a, p->stream);
+  tstop(p);
+}
+
+// the engine path, and every evidence-only evaluation: the m x m products of W as engine launches, then one launch that
+// ships the results
+void finish_engine(gprhip_problem* p, const Ex2<const double>& ex) {
   hipStream_t s = p->stream;
   const int mp = p->mp, m = p->m, d = p->d;
-  const double* ar2_col = ar2 + packed_upper_len(mp);
-  const double* ar2_proj = ar2_col + p->col_rows() * mp;
-  const double* ar2_tail = ar2_proj + (int64_t)p->dbig() * d;
-  const int nkslab = (m + km_slab_rows(m) - 1) / km_slab_rows(m);
-  p->stage = 3;
-  if (light) {
-    GPR_HIP(hipMemcpyAsync(p->res_host + NSCAL, p->info, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-    return;
-  }
-  const bool wdiag = p->want_grad && (p->has_het() || p->has_ms());
-  const int64_t n_a2 = (ar2_tail + A2_TAIL) - ar2_col;  // the exchange-2 buffer from its column block on
-  if (p->want_grad && p->use_small()) {
-    // at most 64 inducing points: the m x m work in one workgroup, which also gathers the exchange-2 tail behind the
-    // result block
-    tstart(p, "finish");
-    SmallFinishArgs a;
-    a.uinv = p->uinv; a.rinv = p->rinv; a.ttil = p->ttil; a.km = p->km; a.Z = p->Z; a.g = ar2;
-    a.ms = p->has_ms() ? p->ms : nullptr;
-    a.m = m; a.mp = mp; a.d = d; a.km_rows = p->has_ms() ? 2 * d + 2 : d + 2;
-    a.wmat = p->wmat; a.kmred = p->kmred; a.wdiag = wdiag ? p->wdiag : nullptr;
-    a.gather_from = ar2_col; a.n_gather = n_a2; a.ex = p->ex_dev + A1_TAIL;
-    launch_small_finish(a, s);
-    tstop(p);
-    const int64_t n_res = p->res_len + A1_TAIL + n_a2;
-    if (n_res * (int64_t)sizeof(double) > 32768) {  // (d > 8 or so: above 32 KB a copy starts 17 us late, a kernel at once)
-      ShipArgs sh;
-      sh.src[0] = p->res_dev; sh.dst[0] = p->res_host; sh.n[0] = n_res;
-      launch_ship(sh, s);
-    } else {
-      GPR_HIP(hipMemcpyAsync(p->res_host, p->res_dev, (size_t)n_res * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    return;
-  }
-  if (p->want_grad && p->use_mid()) {
-    // one or two 128-blocks: the m x m work in two launches of one workgroup per 16 rows (mid.hip), the first of which also
-    // gathers the exchange-2 tail behind the result block
-    tstart(p, "finish");
-    MidFinishArgs a;
-    a.uinv = p->uinv; a.rinv = p->rinv; a.uinvT = p->wtil; a.rinvT = p->binv; a.ttil = p->ttil; a.km = p->km; a.Z = p->Z;
-    a.g = ar2;
-    a.m = m; a.mp = mp; a.d = d; a.km_rows = d + 2;
-    a.wmat = p->wmat; a.kmred = p->kmred; a.wdiag = wdiag ? p->wdiag : nullptr;
-    a.ybuf = p->kj;  // (free after the factorisation of K_m)
-    a.gather_from = ar2_col; a.n_gather = n_a2; a.ex = p->ex_dev + A1_TAIL;
-    // the kernels' last workgroup writes the result block (and, two tiles, the exchange-1 tail) into the pinned mirror itself
-    if (!p->mid_done) {
-      p->mid_done = p->alloc<int>(1);
-      GPR_HIP(hipMemsetAsync(p->mid_done, 0, sizeof(int), s));
-    }
-    a.res_dev = p->res_dev; a.res_host = p->res_host; a.res_total = p->res_len + A1_TAIL + n_a2; a.done_ctr = p->mid_done;
-    if (!p->a1_in_scal) {  // (two tiles: the B~ phase is not the fused single-block kernel that leaves the tail in the result block)
-      a.a1_tail = p->ar1 + packed_upper_len(mp) + mp;
-      a.a1_host = p->ex_host;
-    }
-    launch_mid_finish(a, s);
-    tstop(p);
-    return;
-  }
+  const bool wdiag = wants_wdiag(p);
   if (p->want_grad) {
+    const int nkslab = (m + km_slab_rows(m) - 1) / km_slab_rows(m);
     tstart(p, "finish");
-    launch_build_w(p->binv, p->ttil, ar2, mp, p->wtil, s);
+    launch_build_w(p->binv, p->ttil, ex.tiles, mp, p->wtil, s);
     if (p->multi) launch_targets_w_rankk(p->wtil, mp, p->tg_Tt(), p->multi, s);  // (1/k) T~ T~^T in place of t~ t~^T (zero here)
     GemmArgs y;  // Y = W~ U^-T
     y.A = p->wtil; y.lda = mp; y.B = p->uinv; y.ldb = mp; y.C = p->kj; y.ldc = mp;  // kj is free after potrf; R~ stays in bmat
@@ -1404,12 +1423,33 @@ void do_finish_enqueue(gprhip_problem* p, const double* ar2, bool light = false)
   ShipArgs sh;
   sh.src[0] = p->res_dev; sh.dst[0] = p->res_host; sh.n[0] = res_used;
   if (!p->a1_in_scal) {
-    sh.src[1] = p->ar1 + packed_upper_len(mp) + mp; sh.dst[1] = p->ex_host; sh.n[1] = A1_TAIL;
+    sh.src[1] = ex1_of(p, p->ar1).tail; sh.dst[1] = p->ex_host; sh.n[1] = A1_TAIL;
   }
   if (p->want_grad) {  // (an evidence-only evaluation reads nothing of the exchange-2 buffer)
-    sh.src[2] = ar2_col; sh.dst[2] = p->ex_host + A1_TAIL; sh.n[2] = n_a2;
+    sh.src[2] = ex.col; sh.dst[2] = p->ex_host + A1_TAIL; sh.n[2] = ex.len_from_col();
   }
   launch_ship(sh, s);
+}
+
+// Finish stage, first half: the m x m work of the gradient (W, traces) and the asynchronous copies of everything the
+// host assembly needs, all on the problem's stream; nothing blocks.  `light` (shards of a multi-device context other
+// than the first): only the factorisation flags are fetched -- the reduced buffers are identical on every device, and
+// one device's assembly serves the caller.
+void do_finish_enqueue(gprhip_problem* p, const double* ar2, bool light = false) {
+  if (p->stage != 2) {
+    set_error("gprhip: eval_finish called before eval_pass2");
+    throw HipFail{ST_STATE};
+  }
+  GPR_HIP(hipSetDevice(p->device));
+  p->stage = 3;
+  if (light) {
+    GPR_HIP(hipMemcpyAsync(p->res_host + NSCAL, p->info, 2 * sizeof(int), hipMemcpyDeviceToHost, p->stream));
+    return;
+  }
+  const Ex2<const double> ex = ex2_of(p, ar2);
+  if (p->want_grad && p->use_small()) finish_small(p, ex);
+  else if (p->want_grad && p->use_mid()) finish_mid(p, ex);
+  else finish_engine(p, ex);
 }
 
 // Finish stage, second half: wait for the stream, check the factorisations, assemble l1, l2, dl/dsigma2 and the gradient
@@ -1432,7 +1472,7 @@ void do_finish_collect(gprhip_problem* p, gprhip_result* res, double* grad, doub
   const double* const hwdiag = hkm + p->km_rows() * mp;
   const double* const ha1tail = p->a1_in_scal ? hscal + SC_A1TAIL : p->ex_host;
   const double* const hcol = p->ex_host + A1_TAIL;  // column block + Proj second term + scalar tail of exchange 2
-  const double* const htail = hcol + p->col_rows() * mp + (int64_t)p->dbig() * d;
+  const double* const htail = hcol + ex2_tail_off(p);
   if (hinfo[0] == POTRF_CHAIN_ABORT_CODE || hinfo[1] == POTRF_CHAIN_ABORT_CODE) {
     p->have_v = p->have_k = false;
     set_error("gprhip: internal error: a dependency wait of the one-launch factorisation ran into its bound "
@@ -1507,7 +1547,7 @@ void do_finish_collect(gprhip_problem* p, gprhip_result* res, double* grad, doub
   if (p->has_proj()) {
     const int D = p->D;
     const double* m1 = hcol + (size_t)(d + 1) * mp;       // [big][c] = sum_r x_big,r E_rc
-    const double* term2 = hcol + (size_t)p->col_rows() * mp;  // [big][small]
+    const double* term2 = hcol + ex2_proj_off(p);  // [big][small]
     for (int big = 0; big < D; ++big) {
       for (int small = 0; small < d; ++small) {
         double term1 = 0.0;
@@ -1546,6 +1586,30 @@ void do_finish_collect(gprhip_problem* p, gprhip_result* res, double* grad, doub
   res->n_hypers = pos;
 }
 
+// a buffer of the problem that is being regrown: freed now, not at problem destruction
+template <typename T>
+void release_buf(gprhip_problem* p, T*& q) {
+  if (!q) return;
+  auto it = std::find(p->allocs.begin(), p->allocs.end(), static_cast<void*>(q));
+  if (it != p->allocs.end()) p->allocs.erase(it);
+  (void)hipFree(q);
+  q = nullptr;
+}
+
+// prediction scratch for chunks of `chunk` test points: the points, their projection and three row vectors
+void ensure_predict_scratch(gprhip_problem* p, int64_t chunk) {
+  if (p->xt && p->xt_rows >= chunk) return;
+  GPR_HIP(hipStreamSynchronize(p->stream));
+  release_buf(p, p->xt);
+  release_buf(p, p->pt);
+  release_buf(p, p->prow);
+  p->xt_rows = 0;
+  p->xt = p->alloc<double>(chunk * p->D);
+  p->pt = p->alloc<double>(chunk * p->d);
+  p->prow = p->alloc<double>(3 * chunk);
+  p->xt_rows = chunk;
+}
+
 // Means.calc / Variances.calc (lib/fitc_gp.ml:418-425, :498-518) at nt test points, chunk by chunk,
 // with the m x m state of the last evaluation: V_t = K_tm U^-1, Q_t = V_t R~^-1 (= K_tm R^-1).
 template <typename TS>
@@ -1577,19 +1641,12 @@ void do_predict(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_
   // few inducing points: a chunk is one kernel (small.hip) that keeps its n x m tiles in LDS -- it needs the row buffers
   // only, not the two chunk x mp matrices (268 MB at 131072 rows that a cached small model would pin for nothing)
   const bool small = p->small_path && !p->f32 && p->m <= 64 && mp == TILE && p->d <= 16 && !p->has_ms();
-  auto release = [p](auto*& q) {  // a prediction buffer that is being regrown: freed now, not at problem destruction
-    if (!q) return;
-    auto it = std::find(p->allocs.begin(), p->allocs.end(), static_cast<void*>(q));
-    if (it != p->allocs.end()) p->allocs.erase(it);
-    (void)hipFree(q);
-    q = nullptr;
-  };
   if (want > chunk) {
     const int64_t rows = std::min<int64_t>(131072, std::max(want, 8 * chunk));
     if (!small && p->pred_rows < want) {
       GPR_HIP(hipStreamSynchronize(s));
-      release(p->predA);
-      release(p->predB);
+      release_buf(p, p->predA);
+      release_buf(p, p->predB);
       p->pred_rows = 0;
       p->predA = p->alloc<char>(rows * mp * p->esz);
       p->predB = p->alloc<char>(rows * mp * p->esz);
@@ -1597,17 +1654,7 @@ void do_predict(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_
     }
     chunk = small ? std::max(p->xt_rows >= want ? p->xt_rows : rows, p->chunk) : p->pred_rows;
   }
-  if (!p->xt || p->xt_rows < chunk) {
-    GPR_HIP(hipStreamSynchronize(s));
-    release(p->xt);
-    release(p->pt);
-    release(p->prow);
-    p->xt_rows = 0;
-    p->xt = p->alloc<double>(chunk * p->D);
-    p->pt = p->alloc<double>(chunk * p->d);
-    p->prow = p->alloc<double>(3 * chunk);
-    p->xt_rows = chunk;
-  }
+  ensure_predict_scratch(p, chunk);
   TS* const bufA = static_cast<TS*>(chunk > p->chunk ? p->predA : p->bufA);
   TS* const bufB = static_cast<TS*>(chunk > p->chunk ? p->predB : p->bufB);
   double* rmean = p->prow;
@@ -2049,13 +2096,7 @@ void do_set_targets_many(gprhip_problem* p, const double* targets, int64_t ld, i
       set_error(buf);
       throw HipFail{ST_OOM};
     }
-    auto release = [p](double*& q) {
-      if (!q) return;
-      auto it = std::find(p->allocs.begin(), p->allocs.end(), static_cast<void*>(q));
-      if (it != p->allocs.end()) p->allocs.erase(it);
-      (void)hipFree(q);
-      q = nullptr;
-    };
+    auto release = [p](double*& q) { release_buf(p, q); };
     release(p->tg_y); release(p->tg_w); release(p->tg_small); release(p->tg_part); release(p->tg_rowpart);
     // (the coefficient block went with tg_small.  multi_state stays: the single-target t / w are no more valid than before)
     p->tg_coeffs = false;
@@ -2145,22 +2186,7 @@ void do_predict_targets(gprhip_problem* p, const double* test_inputs, int64_t ld
   hipStream_t s = p->stream;
   const int mp = p->mp, k = p->tg_k;
   const int64_t chunk = p->chunk, npad = p->npad();
-  if (!p->xt || p->xt_rows < chunk) {
-    GPR_HIP(hipStreamSynchronize(s));
-    auto release = [p](double*& q) {
-      if (!q) return;
-      auto it = std::find(p->allocs.begin(), p->allocs.end(), static_cast<void*>(q));
-      if (it != p->allocs.end()) p->allocs.erase(it);
-      (void)hipFree(q);
-      q = nullptr;
-    };
-    release(p->xt); release(p->pt); release(p->prow);
-    p->xt_rows = 0;
-    p->xt = p->alloc<double>(chunk * p->D);
-    p->pt = p->alloc<double>(chunk * p->d);
-    p->prow = p->alloc<double>(3 * chunk);
-    p->xt_rows = chunk;
-  }
+  ensure_predict_scratch(p, chunk);
   double* const K = static_cast<double*>(p->bufA);
   for (int64_t lo = 0; lo < nt; lo += chunk) {
     const int rows = (int)std::min<int64_t>(chunk, nt - lo);

@@ -1996,6 +1996,51 @@ def test_shards_on_both_sides_of_the_two_tile_row_limit():
     assert M.grad_ok(ev.grad, ref["grad"], fams, TOL_GRAD, cond=cond) and M.vec_ok("coeffs", ev.coeffs, ref["coeffs"], TOL_COEFF)
 
 
+# ("kernel_p1_syrk_B" is the level-1 event pair around the pass-1 Gram launch, which level 2 includes; tcollect lists it first)
+_ENGINE_P1 = ["kernel_p1_syrk_B", "km_chol", "p1_cov", "p1_trmm_V", "p1_rows", "p1_syrk_B", "b_chol", "inverses", "p2_trmm_Q", "p2_rows"]
+# (n, m, d, chunk_rows, switches, stages of a gradient evaluation, stages of the reuse_v re-evaluation or None)
+_STAGE_ORDER = {
+    "small": (300, 20, 3, 0, {}, ["km_chol", "p1_small", "b_chol", "p2_small", "finish"], None),
+    "one_tile": (300, 100, 3, 0, {}, ["km_chol", "p1_mid", "b_chol", "p2_mid", "finish"], None),
+    "two_tiles": (600, 200, 3, 0, {}, ["kernel_p1_syrk_B", "km_chol", "p1_mid", "p1_syrk_B", "b_chol", "p2_mid", "p2_syrk_W", "finish"],
+                  ["km_chol", "p1_rows", "p1_syrk_B", "b_chol", "p2_mid", "p2_syrk_W", "finish"]),
+    "two_tiles_engine_gram": (600, 200, 3, 0, {"GPRHIP_MID_GRAM": "0"},
+                              ["kernel_p1_syrk_B", "km_chol", "p1_mid", "p1_syrk_B", "b_chol", "p2_mid", "p2_syrk_W", "finish"], None),
+    "engine_two_launch_x": (1500, 300, 3, 512, {"GPRHIP_MERGED_X": "0"},
+                            _ENGINE_P1 + ["p2_trmm_S", "p2_trmm_X", "p2_grad", "p2_syrk_W", "finish"], None),
+    "engine_two_phase_x": (1500, 300, 3, 512, {"GPRHIP_MERGED_X": "2"},
+                           _ENGINE_P1 + ["p2_trmm_SX", "p2_grad", "p2_syrk_W", "finish"], None),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", sorted(_STAGE_ORDER))
+def test_stage_order_of_every_evaluation_path(case, monkeypatch):
+    """The order in which a gradient evaluation enters its stages (last_timings() under set_timing(2) lists every stage once,
+    by first entry), per path: small.hip, mid.hip with one tile, with two tiles and its own Gram launch pair, with two tiles and
+    the engine's Gram launch, the engine over three ragged chunks with either X product -- and the re-weighted (reuse_v)
+    evaluation of a two-tile problem, whose rows go through the engine's row kernel and whose Gram accumulation through the
+    pair again.  The lists were recorded from the driver before each path got a function of its own."""
+    n, m, d, chunk_rows, env, expect, expect_reuse = _STAGE_ORDER[case]
+    for k_, v_ in env.items():
+        monkeypatch.setenv(k_, v_)  # read when the problem is created
+    X, y, Z = synth(11, n, m, d)
+    hyp = dict(log_ell=0.5 * np.log(d) + 0.1, log_sf2=-0.1, sigma2=0.2, inducing=Z)
+    p = gpr_amd.Problem(gpr_amd.COV_SE_ISO, n, d, d, m, chunk_rows=chunk_rows)
+    p.set_inputs(X)
+    p.set_targets(y)
+    p.set_timing(2)
+    p.eval(**hyp)
+    stages = list(p.last_timings())
+    reuse = None
+    if expect_reuse is not None:
+        p.eval(**dict(hyp, sigma2=0.4), reuse_v=True)
+        reuse = list(p.last_timings())
+    p.close()
+    assert stages == expect, stages
+    assert reuse == expect_reuse, reuse
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed", range(3100, 3106))
 def test_random_small_shapes_through_the_context(seed):
