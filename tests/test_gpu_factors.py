@@ -30,7 +30,9 @@ import gpr_amd
 from gpr_amd import _lib
 from oracle import fitc_oracle as O
 from tests import margins as M
-from tests.util import synth
+from tests.util import factor_case
+from tests.util import oracle_km_full as _oracle_km_full
+from tests.util import taken as _taken
 
 gpu = pytest.mark.gpu
 
@@ -51,10 +53,6 @@ def _path_of(m):
     return "small" if m <= 64 else ("mid" if m <= 256 else "engine")
 
 
-def _taken(stages):
-    return "small" if "p1_small" in stages else ("mid" if "p1_mid" in stages else ("engine" if "p1_trmm_V" in stages else "?"))
-
-
 # ---- 1. factor residuals ---------------------------------------------------------------------------------------------------
 M_SMALL = [1, 2, 15, 16, 17, 33, 48, 49, 63, 64]
 M_MID = [65, 80, 81, 127, 128, 129, 255, 256]
@@ -64,46 +62,15 @@ M_INVERSE = [49, 64, 65, 129, 273]
 N_TRAIN = 800
 
 
-def _oracle_km_full(ok, Z):
-    """K_m as the oracle builds it (heteroskedastic noise on the diagonal, no jitter), full symmetric"""
-    km, _ = O.spec_calc_shared_upper(ok, np.asfortranarray(Z))
-    km = np.triu(np.nan_to_num(km, nan=0.0))
-    return km + np.triu(km, 1).T
-
-
-def _cond(a):
-    w = np.linalg.eigvalsh(a)
-    return float(w[-1] / w[0]) if w[0] > 0 else np.inf
-
-
 @functools.lru_cache(maxsize=None)
 def _factor_case(kind, m):
     """Inputs, targets, inducing points, Problem.eval arguments, the oracle's kernel, cond(K_m + jitter I).  The tests
     assert cond <= COND_MAX = 1e6, the bound the comparison of R relies on; the length scale is CHOSEN a decade inside it,
-    as the largest of 0.8^k at which the oracle's K_m + jitter I has a condition number of at most 1e5 (asserted here: the
-    search may not run out).  How far from the identity the factors then are -- the share of entries above the diagonal of
-    U beyond 1e-8, the largest of them -- is recorded with every factor_U figure (profiles/factor_margins.txt)."""
-    d = 2 if kind == "iso" else 3
-    X, y, Z = synth(900 + m, N_TRAIN, m, d)
-    het = None if kind == "iso" else np.random.default_rng(m).uniform(-7.0, -4.0, size=m)
-    ell = 1.0
-    for _ in range(40):
-        if kind == "iso":
-            ok, Zs = O.SeIsoKernel(float(np.log(ell)), 0.0), Z
-        else:  # Cov_se_fat has unit length scales: the points carry the scale
-            ok, Zs = O.SeFatKernel(d, 0.0, None, het, None), np.asfortranarray(Z / ell)
-        cond = _cond(_oracle_km_full(ok, Zs) + O.CHOLESKY_JITTER * np.eye(m))
-        if cond <= 1e5:
-            break
-        ell *= 0.8
-    assert cond <= 1e5, (kind, m, ell, cond)
-    if kind == "iso":
-        args = dict(log_ell=float(np.log(ell)), log_sf2=0.0)
-        Xs = X
-    else:
-        args = dict(log_sf2=0.0, log_hetero_skedasticity=het)
-        Xs = np.asfortranarray(X / ell)
-    return Xs, y, Zs, args, ok, cond
+    as the largest of 0.8^k at which the oracle's K_m + jitter I has a condition number of at most 1e5 (asserted in
+    tests/util.py::factor_case: the search may not run out).  How far from the identity the factors then are -- the share
+    of entries above the diagonal of U beyond 1e-8, the largest of them -- is recorded with every factor_U figure
+    (profiles/factor_margins.txt)."""
+    return factor_case("iso" if kind == "iso" else "fat_het", N_TRAIN, m)
 
 
 @functools.lru_cache(maxsize=None)

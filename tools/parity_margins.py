@@ -1,6 +1,8 @@
 """Table of achieved parity errors against their asserted bounds, from the log tests/margins.py writes.
     usage (GPU box): GPR_MARGINS_LOG=gpurun_out/margins.jsonl python -m pytest tests -m gpu -q
                      python3 tools/parity_margins.py gpurun_out/margins.jsonl > profiles/r06_parity_margins.txt
+    profiles/row_operand_margins.txt: the log of tests/test_gpu_row_operands.py's CPU halves (the oracle against its 80-bit
+    restatement, "oracle_*") followed by the log of its GPU halves.
 One line per (test function, quantity, bound): number of checks, worst error, bound, bound / worst.  The summary at the
 end lists, per (quantity, bound), the worst error over the whole run -- the figure the TOL_* constants of
 tests/test_gpu_parity.py are set from (<= 10 x the worst observed, rounded up to one digit)."""
