@@ -82,6 +82,7 @@ class TargetsResult(C.Structure):
 
 
 MAX_TARGETS = 16  # GPRHIP_MAX_TARGETS
+MAX_BATCH = 64    # GPRHIP_MAX_BATCH
 
 # name -> (restype, argtypes); the single source of truth for tests/test_abi.py as well
 _dp = C.POINTER(C.c_double)
@@ -140,6 +141,12 @@ SIGNATURES = {
     "gprhip_sharded_train_stats": (C.c_int, [_vp, _dp, _dp]),
     "gprhip_sharded_comm_stats": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_float)]),
     "gprhip_sharded_set_timing": (C.c_int, [_vp, C.c_int]),
+    "gprhip_batch_create": (C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
+    "gprhip_batch_destroy": (None, [_vp]),
+    "gprhip_batch_lanes": (C.c_int, [_vp]),
+    "gprhip_batch_lane": (_vp, [_vp, C.c_int]),
+    "gprhip_batch_eval": (C.c_int, [_vp, C.c_int, C.POINTER(Hypers), C.c_int, C.POINTER(Result), _dp, C.c_int64, _dp,
+                                    C.POINTER(C.c_int)]),
     "gprhip_last_error": (C.c_char_p, []),
     "gprhip_version": (C.c_char_p, []),
 }

@@ -593,6 +593,16 @@ __global__ __launch_bounds__(PT) void potrf_fused_kernel(PotrfFuse f, double* __
   potrf_diag_body<1>(A, NB, 0, dinv, info, 64, m_real, f, PotrfKm{});
 }
 
+// one lane per blockIdx.y (gridDim.x = 1, as the single launches), the lane's arguments from a device array: a uniform read
+__global__ __launch_bounds__(PT) void potrf_km_batch_kernel(const PotrfKmLane* __restrict__ lanes, int64_t stride) {
+  const PotrfKmLane a = lane_args(lanes, stride);
+  potrf_diag_body<2>(a.A, NB, 0, a.Xinv, a.info, 64, a.g.m, PotrfFuse{}, a.g);
+}
+__global__ __launch_bounds__(PT) void potrf_fused_batch_kernel(const PotrfFuseLane* __restrict__ lanes, int64_t stride) {
+  const PotrfFuseLane a = lane_args(lanes, stride);
+  potrf_diag_body<1>(a.A, NB, 0, a.Xinv, a.info, 64, a.m_real, a.f, PotrfKm{});
+}
+
 // ---- blocked factorisation without the engine: panel solve and trailing update of one 128-row step
 //
 // A step of the right-looking factorisation is a latency chain (diagonal block -> panel -> trailing blocks -> next
@@ -1162,6 +1172,10 @@ static void potrf_attrs() {
                                 hipFuncAttributeMaxDynamicSharedMemorySize, POTRF_LDS));
     GPR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&potrf_km_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, POTRF_LDS));
+    GPR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&potrf_km_batch_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, POTRF_LDS));
+    GPR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&potrf_fused_batch_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, POTRF_LDS));
     GPR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&potrf_panel_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, PANEL_LDS));
 #ifdef GPRHIP_LAB
@@ -1178,6 +1192,16 @@ void launch_potrf_km(const PotrfKm& g, double* A, double* Xinv, int* info, hipSt
 void launch_potrf_fused(const PotrfFuse& f, double* A, double* Xinv, int* info, int m_real, hipStream_t s) {
   potrf_attrs();
   hipLaunchKernelGGL(potrf_fused_kernel, dim3(1), dim3(PT), POTRF_LDS, s, f, A, Xinv, info, m_real);
+  GPR_HIP(hipGetLastError());
+}
+void launch_potrf_km_batch(const PotrfKmLane* d_lanes, int count, int64_t stride, hipStream_t s) {
+  potrf_attrs();
+  hipLaunchKernelGGL(potrf_km_batch_kernel, dim3(1, count), dim3(PT), POTRF_LDS, s, d_lanes, stride);
+  GPR_HIP(hipGetLastError());
+}
+void launch_potrf_fused_batch(const PotrfFuseLane* d_lanes, int count, int64_t stride, hipStream_t s) {
+  potrf_attrs();
+  hipLaunchKernelGGL(potrf_fused_batch_kernel, dim3(1, count), dim3(PT), POTRF_LDS, s, d_lanes, stride);
   GPR_HIP(hipGetLastError());
 }
 void potrf_fetch_timestamps(unsigned long long* out64) {

@@ -346,7 +346,7 @@ void launch_km_traces(const double* W, const double* km, const double* Z, int m,
 // block on) written into the pinned host mirror by a kernel instead of by hipMemcpyAsync: behind a kernel a device-to-host
 // copy of more than 32 KB (or a second and third one) starts 17-18 us late on this runtime (profiles/r06_timeline_*), a
 // kernel starts at once, and a few workgroups storing over the host link move these 40-600 KB as fast as the copy engine.
-__global__ __launch_bounds__(256) void ship_kernel(ShipArgs a) {
+__device__ __forceinline__ void ship_body(const ShipArgs& a) {
   const int64_t stride = (int64_t)gridDim.x * 256;
 #pragma unroll
   for (int b = 0; b < 3; ++b) {
@@ -355,6 +355,19 @@ __global__ __launch_bounds__(256) void ship_kernel(ShipArgs a) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n[b]; i += stride)
       __builtin_nontemporal_store(__builtin_nontemporal_load(src + i), dst + i);
   }
+}
+
+__global__ __launch_bounds__(256) void ship_kernel(ShipArgs a) { ship_body(a); }
+__global__ __launch_bounds__(256) void ship_batch_kernel(const ShipArgs* __restrict__ lanes, int64_t stride) {
+  const ShipArgs a = lane_args(lanes, stride);
+  ship_body(a);
+}
+
+void launch_ship_batch(const ShipArgs* d_lanes, int count, int64_t stride, int64_t n_max, hipStream_t s) {
+  if (n_max <= 0 || count < 1) return;
+  const int grid = (int)std::min<int64_t>(32, (n_max + 2047) / 2048);
+  hipLaunchKernelGGL(ship_batch_kernel, dim3(std::max(grid, 1), count), dim3(256), 0, s, d_lanes, stride);
+  GPR_HIP(hipGetLastError());
 }
 
 void launch_ship(const ShipArgs& a, hipStream_t s) {

@@ -92,6 +92,11 @@ struct Timer {
 }  // namespace
 
 struct gprhip_problem {
+  // A lane of a gprhip_batch (lane_of = the problem the batch was made on): X, y and the stream are that problem's, the
+  // parameter block (hy_dev / hy_host) is a slice of the batch's one upload block -- none of them is released with the lane
+  gprhip_problem* lane_of = nullptr;
+  bool is_lane = false;
+  std::vector<gprhip_batch*> batches;  // the batches that borrow this problem (told when it is destroyed)
   int device = 0, kind = 0;
   int64_t n = 0;
   int D = 0, d = 0, m = 0, mp = 0;
@@ -270,7 +275,33 @@ struct gprhip_problem {
   bool mid_pair() const { return use_mid() && mp > TILE && use_mid_gram(); }
 };
 
+// Several evaluations side by side (gprhip_batch_*): one internal problem per lane on the parent's device and stream, and ONE
+// upload block -- per lane [parameter block (upload_hypers' layout) | the argument structs of the lane's eight launches],
+// `stride` bytes apiece, so that the lanes in use are one contiguous transfer and lane j's structs lie at a fixed offset
+// behind lane 0's (the batched kernels index them with blockIdx.y * stride)
+struct gprhip_batch {
+  gprhip_problem* parent = nullptr;  // null once the parent has been destroyed
+  std::vector<gprhip_problem*> lanes;
+  char *up_host = nullptr, *up_dev = nullptr;
+  int64_t stride = 0;
+  int64_t o_km = 0, o_p1 = 0, o_r1 = 0, o_fuse = 0, o_p2 = 0, o_r2 = 0, o_fin = 0, o_ship = 0;  // byte offsets in a lane's slice
+  template <typename T> T* host(int j, int64_t off) const { return reinterpret_cast<T*>(up_host + j * stride + off); }
+  template <typename T> const T* dev(int64_t off) const { return reinterpret_cast<const T*>(up_dev + off); }
+};
+
 namespace {
+
+void batch_orphan_all(gprhip_problem* p) {
+  for (gprhip_batch* b : p->batches) {
+    b->parent = nullptr;
+    for (gprhip_problem* l : b->lanes) {
+      l->stream = nullptr;
+      l->X = l->y = nullptr;
+      l->have_inputs = l->have_targets = l->have_model = false;
+    }
+  }
+  p->batches.clear();
+}
 
 template <typename TS> const TS* inv_u(const gprhip_problem* p);
 template <> const double* inv_u<double>(const gprhip_problem* p) { return p->uinv; }
@@ -484,7 +515,7 @@ void triu_xxt(gprhip_problem* p, const double* X, double* C, hipStream_t st) {
   }
 }
 
-void upload_hypers(gprhip_problem* p, const gprhip_hypers* h) {
+void check_hypers(const gprhip_problem* p, const gprhip_hypers* h) {
   if (!h || !h->inducing) {
     set_error("gprhip: hypers/inducing pointer is NULL");
     throw HipFail{ST_BAD_ARG};
@@ -509,14 +540,16 @@ void upload_hypers(gprhip_problem* p, const gprhip_hypers* h) {
     set_error("gprhip: log_multiscales_m05 given for Cov_se_iso");
     throw HipFail{ST_BAD_ARG};
   }
+}
+
+// the host half of an upload: p->h, p->cp and the pinned parameter block; returns the doubles of the block in use (a prefix)
+int64_t stage_hypers(gprhip_problem* p, const gprhip_hypers* h) {
   p->h = *h;                // (after every argument check: a refused call leaves no borrowed pointer behind)
   p->h.inducing = nullptr;  // borrowed; the padded copy lives in hZ
   // the optional arrays are presence flags from here on, pointing at the library's own pinned copies (filled below)
   p->h.tproj = h->tproj ? p->hTproj : nullptr;
   p->h.log_hetero_skedasticity = h->log_hetero_skedasticity ? p->hHet : nullptr;
   p->h.log_multiscales_m05 = h->log_multiscales_m05 ? p->hMs : nullptr;
-  // the pinned block may still be the source of the previous evaluation's transfer (a pass 1 repeated without a finish)
-  GPR_HIP(hipEventSynchronize(p->ev_hy));
   int64_t used = (int64_t)p->mp * p->d + 64;  // doubles of the block this evaluation uploads (a prefix)
   if (h->log_hetero_skedasticity) {  // Kernel.create: Vec.map exp, lib/cov_se_fat.ml:63-65
     for (int i = 0; i < p->m; ++i) p->hHet[i] = std::exp(h->log_hetero_skedasticity[i]);
@@ -557,6 +590,14 @@ void upload_hypers(gprhip_problem* p, const gprhip_hypers* h) {
     p->h.tproj = p->hTproj;
     used = std::max<int64_t>(used, (p->hTproj - p->hy_host) + (int64_t)p->D * p->d);
   }
+  return used;
+}
+
+void upload_hypers(gprhip_problem* p, const gprhip_hypers* h) {
+  check_hypers(p, h);
+  // the pinned block may still be the source of the previous evaluation's transfer (a pass 1 repeated without a finish)
+  GPR_HIP(hipEventSynchronize(p->ev_hy));
+  const int64_t used = stage_hypers(p, h);
   GPR_HIP(hipMemcpyAsync(p->hy_dev, p->hy_host, (size_t)used * sizeof(double), hipMemcpyHostToDevice, p->stream));
   GPR_HIP(hipEventRecord(p->ev_hy, p->stream));
   if (h->tproj) launch_project(p->X, p->n, p->D, p->d, p->tproj, p->P, p->stream);
@@ -1586,6 +1627,202 @@ void do_finish_collect(gprhip_problem* p, gprhip_result* res, double* grad, doub
   res->n_hypers = pos;
 }
 
+// ---- several hyper-parameter sets in one pass (gprhip_batch_eval): the small path's chain, each launch once for all lanes
+// Bytes one lane adds to the device: a problem's resident set without the inputs and targets it borrows, plus what the small
+// path otherwise allocates at its first evaluation (the V store is in the plan; the partial sums and the K read-back are not)
+int64_t batch_lane_bytes(const gprhip_problem* p) {
+  gprhip_memory_plan_t plan;
+  memory_plan(p->kind, GPRHIP_F64, p->n, p->D, p->d, p->m, p->chunk, &plan);
+  const int64_t npad = (int64_t)p->nchunks * p->chunk;
+  return plan.total - (p->n * p->D + npad) * 8 + small_part_len(p->d, p->D) * 8 + round_up(p->n, TILE) * 64 * 8;
+}
+
+// everything gprhip_batch_eval refuses, before anything is staged or enqueued
+void batch_check(const gprhip_batch* b, int count, const gprhip_hypers* h, const gprhip_result* res, const double* grad,
+                 int64_t ldg, int want_grad, const int* status) {
+  if (!b || !h || !res || !status || count < 1 || count > (int)b->lanes.size()) {
+    set_error("gprhip_batch_eval: invalid arguments (need 1 <= count <= the batch's lanes, h, res and status for every lane)");
+    throw HipFail{ST_BAD_ARG};
+  }
+  const gprhip_problem* p = b->parent;
+  if (!p) {
+    set_error("gprhip_batch_eval: the problem this batch was made on has been destroyed");
+    throw HipFail{ST_STATE};
+  }
+  for (int j = 0; j < count; ++j) {
+    check_hypers(b->lanes[j], &h[j]);
+    if (h[j].reuse_v) {
+      set_error("gprhip_batch_eval: reuse_v is not available inside a batch");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if ((h[j].tproj != nullptr) != (h[0].tproj != nullptr) ||
+        (h[j].log_hetero_skedasticity != nullptr) != (h[0].log_hetero_skedasticity != nullptr) ||
+        (h[j].log_multiscales_m05 != nullptr) != (h[0].log_multiscales_m05 != nullptr) ||
+        (h[j].variational != 0) != (h[0].variational != 0) || (h[j].model_only != 0) != (h[0].model_only != 0)) {
+      set_error("gprhip_batch_eval: the lanes of one call must share their option shape (tproj, log_hetero_skedasticity, "
+                "log_multiscales_m05 each given for all or none; variational and model_only equal)");
+      throw HipFail{ST_BAD_ARG};
+    }
+  }
+  if (!small_path_fits(p->m, p->mp, p->d, h[0].tproj ? p->D : 0, p->n, h[0].log_multiscales_m05 != nullptr)) {
+    set_error("gprhip_batch_eval: these hypers are outside the small path (at most 64 input dimensions in front of a "
+              "projection, multiscales with d <= 8): evaluate them one by one with gprhip_eval");
+    throw HipFail{ST_BAD_ARG};
+  }
+  if (want_grad) {
+    const gprhip_problem* l = b->lanes[0];
+    const int64_t nh = gprhip_n_hypers(l, (h[0].tproj ? 1 : 0) | (h[0].log_hetero_skedasticity ? 2 : 0) |
+                                              (h[0].log_multiscales_m05 ? 4 : 0));
+    if (!grad || ldg < nh) {
+      set_error("gprhip_batch_eval: want_grad needs grad with ldg >= the number of hyper-parameters");
+      throw HipFail{ST_BAD_ARG};
+    }
+  }
+  if (!p->have_inputs || (!p->have_targets && !h[0].model_only)) {
+    set_error("gprhip: inputs/targets not set");
+    throw HipFail{ST_STATE};
+  }
+}
+
+// Lane l's part of the upload block and its state for this evaluation: what do_pass1 / do_pass2 / do_finish_enqueue decide on
+// the host for a small-path evaluation, with every launch's arguments written into the lane's structs instead of launched
+void batch_stage_lane(gprhip_batch* b, int j, const gprhip_hypers* h, int want_grad) {
+  gprhip_problem* l = b->lanes[j];
+  const gprhip_problem* p = b->parent;
+  l->have_inputs = p->have_inputs;
+  l->have_targets = p->have_targets;
+  // (as do_pass1) the state of the lane's previous evaluation is void from here on
+  l->have_model = l->have_factors = false;
+  l->multi_state = false;
+  l->tg_coeffs = false;
+  l->x_last = nullptr;
+  l->cond_km = -1.0;
+  l->have_v = l->have_k = l->small_k_valid = false;
+  stage_hypers(l, h);
+  l->want_grad = want_grad;
+  l->n_total = l->n;
+  const Ex1<double> e1 = ex1_of(l, l->ar1);
+  const Ex2<double> e2 = ex2_of(l, l->ar2);
+  {  // K_m and its factor (pass1_km_chol; with multiscales the lane takes the single evaluation's launches instead)
+    PotrfKmLane& k = *b->host<PotrfKmLane>(j, b->o_km);
+    k = PotrfKmLane{};
+    k.g.cp = l->cp; k.g.Z = l->Z; k.g.m = l->m; k.g.d = l->d; k.g.jitter = l->h.jitter;
+    k.g.het = l->has_het() ? l->het : nullptr; k.g.km = l->km;
+    k.A = l->umat; k.Xinv = l->uinv; k.info = l->info;
+  }
+  {  // pass 1 and its reduction (pass1_small)
+    SmallPass1Args& a = *b->host<SmallPass1Args>(j, b->o_p1);
+    fill_row_pass1(l, a);
+    a.part = l->small_part;
+    a.Kout = (l->d <= 8 && !l->has_ms()) ? l->small_k : nullptr;
+    l->small_k_valid = a.Kout != nullptr;
+    SmallReduce1Args& r = *b->host<SmallReduce1Args>(j, b->o_r1);
+    r.part = a.part; r.ng = small_pass1_groups(a.rows_p); r.mp = a.mp; r.tile = e1.tiles; r.cvec = e1.c; r.tail = e1.tail;
+  }
+  {  // B~, its factor and the m-vectors (pass2_b_chol, single block)
+    l->a1_in_scal = true;
+    PotrfFuseLane& f = *b->host<PotrfFuseLane>(j, b->o_fuse);
+    f = PotrfFuseLane{};
+    f.f.src = e1.tiles; f.f.cvec = e1.c; f.f.tail_in = e1.tail; f.f.tail_out = l->scal + SC_A1TAIL;
+    f.f.uinv = l->uinv; f.f.bvec = l->bvec; f.f.ttil = l->ttil; f.f.tvec = l->tvec;
+    f.f.logdet = l->scal + SC_LOGDET_B; f.f.bb = l->scal + SC_BB;
+    f.A = l->bmat; f.Xinv = l->rinv; f.info = l->info + 1; f.m_real = l->m;
+  }
+  ShipArgs& sh = *b->host<ShipArgs>(j, b->o_ship);
+  sh = ShipArgs{};
+  sh.src[0] = l->res_dev; sh.dst[0] = l->res_host;
+  if (want_grad) {
+    l->merged_x = false;
+    SmallPass2Args& a = *b->host<SmallPass2Args>(j, b->o_p2);  // pass 2 and its reduction (pass2_small)
+    fill_row_pass2(l, a);
+    a.uinv = l->uinv;
+    a.Kin = (l->small_k_valid && l->d <= 8 && !l->has_ms()) ? l->small_k : nullptr;
+    a.part = l->small_part;
+    l->x_last = a.X;
+    SmallReduce2Args& r = *b->host<SmallReduce2Args>(j, b->o_r2);
+    r.part = a.part; r.ng = small_pass2_groups(a.rows_p); r.mp = a.mp; r.d = a.d; r.D = a.D; r.ms = l->has_ms() ? 1 : 0;
+    r.col_rows = (int)l->col_rows(); r.tile = e2.tiles; r.colblk = e2.col; r.proj = e2.proj; r.tail = e2.tail;
+    SmallFinishArgs& fa = *b->host<SmallFinishArgs>(j, b->o_fin);  // finish_small
+    fa.uinv = l->uinv; fa.rinv = l->rinv; fa.ttil = l->ttil; fa.km = l->km; fa.Z = l->Z; fa.g = e2.tiles;
+    fa.ms = l->has_ms() ? l->ms : nullptr;
+    fa.m = l->m; fa.mp = l->mp; fa.d = l->d; fa.km_rows = l->has_ms() ? 2 * l->d + 2 : l->d + 2;
+    fa.wmat = l->wmat; fa.kmred = l->kmred; fa.wdiag = wants_wdiag(l) ? l->wdiag : nullptr;
+    fa.gather_from = e2.col; fa.n_gather = e2.len_from_col(); fa.ex = l->ex_dev + A1_TAIL;
+    sh.n[0] = l->res_len + A1_TAIL + e2.len_from_col();  // (the lane's own pinned block, written by the ship launch)
+  } else {
+    sh.n[0] = NSCAL + 2 + l->mp;  // (finish_engine's evidence-only block: scalars, flags, t)
+  }
+}
+
+void batch_eval(gprhip_batch* b, int count, const gprhip_hypers* h, int want_grad, gprhip_result* res, double* grad,
+                int64_t ldg, double* coeffs, int* status) {
+  batch_check(b, count, h, res, grad, ldg, want_grad, status);
+  gprhip_problem* const p = b->parent;
+  gprhip_problem* const l0 = b->lanes[0];  // (its timer carries the batched stages)
+  GPR_HIP(hipSetDevice(p->device));
+  hipStream_t s = p->stream;
+  want_grad = want_grad != 0;
+  for (int j = 0; j < count; ++j) batch_stage_lane(b, j, &h[j], want_grad);
+  // one transfer: the parameter blocks and the argument structs of the lanes in use (the previous batch evaluation ended
+  // in a wait for the stream, so the pinned block is free)
+  GPR_HIP(hipMemcpyAsync(b->up_dev, b->up_host, (size_t)(b->stride * count), hipMemcpyHostToDevice, s));
+  if (l0->has_proj())
+    for (int j = 0; j < count; ++j) {
+      gprhip_problem* l = b->lanes[j];
+      launch_project(l->X, l->n, l->D, l->d, l->tproj, l->P, s);
+    }
+  const int64_t st = b->stride;
+  tstart(l0, "batch_km_chol");
+  if (l0->has_ms()) {  // (K_m with multiscales is built by the launch the single evaluation uses, lane by lane)
+    for (int j = 0; j < count; ++j) {
+      gprhip_problem* l = b->lanes[j];
+      launch_cov_upper(l->cp, l->Z, l->m, l->mp, l->d, l->h.jitter, l->has_het() ? l->het : nullptr, l->km, l->umat, s);
+      potrf_trtri(l, l->umat, l->uinv, l->wmat, l->info);
+    }
+  } else {
+    launch_potrf_km_batch(b->dev<PotrfKmLane>(b->o_km), count, st, s);
+  }
+  tstop(l0);
+  tstart(l0, "batch_p1");
+  launch_small_pass1_batch(*b->host<SmallPass1Args>(0, b->o_p1), b->dev<SmallPass1Args>(b->o_p1),
+                           b->dev<SmallReduce1Args>(b->o_r1), count, st, s);
+  tstop(l0);
+  tstart(l0, "batch_b_chol");
+  launch_potrf_fused_batch(b->dev<PotrfFuseLane>(b->o_fuse), count, st, s);
+  tstop(l0);
+  if (want_grad) {
+    tstart(l0, "batch_p2");
+    launch_small_pass2_batch(*b->host<SmallPass2Args>(0, b->o_p2), (int)l0->col_rows(), b->dev<SmallPass2Args>(b->o_p2),
+                             b->dev<SmallReduce2Args>(b->o_r2), count, st, s);
+    tstop(l0);
+    tstart(l0, "batch_finish");
+    launch_small_finish_batch(*b->host<SmallFinishArgs>(0, b->o_fin), b->dev<SmallFinishArgs>(b->o_fin), count, st, s);
+  } else {
+    tstart(l0, "batch_finish");
+  }
+  // every lane's results into its own pinned block by one launch, whatever their size
+  launch_ship_batch(b->dev<ShipArgs>(b->o_ship), count, st, b->host<ShipArgs>(0, b->o_ship)->n[0], s);
+  tstop(l0);
+  for (int j = 0; j < count; ++j) {
+    b->lanes[j]->stage = 3;
+    b->lanes[j]->have_v = true;  // (revoked by the collect if the lane's factorisation was refused)
+  }
+  GPR_HIP(hipStreamSynchronize(s));  // the one wait of the batch
+  std::string first_error;
+  for (int j = 0; j < count; ++j) {
+    try {
+      do_finish_collect(b->lanes[j], &res[j], grad ? grad + (int64_t)j * ldg : nullptr,
+                        coeffs ? coeffs + (int64_t)j * p->m : nullptr);
+      status[j] = GPRHIP_OK;
+    } catch (const HipFail& e) {
+      if (e.status != ST_NOT_POSDEF) throw;
+      status[j] = GPRHIP_ENOTPOSDEF;
+      if (first_error.empty()) first_error = last_error();
+    }
+  }
+  if (!first_error.empty()) set_error(first_error);
+}
+
 // a buffer of the problem that is being regrown: freed now, not at problem destruction
 template <typename T>
 void release_buf(gprhip_problem* p, T*& q) {
@@ -2268,8 +2505,26 @@ int gprhip_problem_create(int device, int cov_kind, int64_t n, int D, int d, int
   return gprhip_problem_create_ex(device, cov_kind, GPRHIP_F64, n, D, d, m, chunk_rows, out);
 }
 
+// share (lanes of a batch): the problem whose inputs, targets and stream the new one borrows, and its slice of the batch's
+// parameter blocks; the batch has compared the memory of all its lanes with the device's before the first one is made
+struct LaneShare {
+  gprhip_problem* parent;
+  double *hy_dev, *hy_host;
+};
+static int64_t hy_block_len(int cov_kind, int mp, int D, int d) {
+  const bool fat = cov_kind == GPRHIP_COV_SE_FAT;
+  return (int64_t)mp * d + 64 + (fat ? round_up((int64_t)D * d, 2) + mp + (int64_t)mp * d : 0);
+}
+static int problem_create_impl(int device, int cov_kind, int precision, int64_t n, int D, int d, int m, int64_t chunk_rows,
+                               gprhip_problem** out, const LaneShare* share);
+
 int gprhip_problem_create_ex(int device, int cov_kind, int precision, int64_t n, int D, int d, int m,
                              int64_t chunk_rows, gprhip_problem** out) {
+  return problem_create_impl(device, cov_kind, precision, n, D, d, m, chunk_rows, out, nullptr);
+}
+
+static int problem_create_impl(int device, int cov_kind, int precision, int64_t n, int D, int d, int m, int64_t chunk_rows,
+                               gprhip_problem** out, const LaneShare* share) {
   return guarded([&] {
     if (precision != GPRHIP_F64 && precision != GPRHIP_F32_BULK) {
       set_error("gprhip_problem_create_ex: unknown precision");
@@ -2296,7 +2551,11 @@ int gprhip_problem_create_ex(int device, int cov_kind, int precision, int64_t n,
     p->nchunks = z.nchunks;
     p->slice_rows = z.slice_rows;
     p->kslices = z.kslices;
-    {  // the whole resident set of the problem against what the device has free, BEFORE anything is allocated: a shard that
+    if (share) {
+      p->is_lane = true;
+      p->lane_of = share->parent;
+    }
+    if (!share) {  // the whole resident set of the problem against what the device has free, BEFORE anything is allocated: a shard that
        // cannot hold its V store fails here, by name and with the figures, not in the first evaluation's hipMalloc
       gprhip_memory_plan_t plan;
       memory_plan(cov_kind, precision, n, D, d, m, chunk_rows, &plan);
@@ -2339,7 +2598,8 @@ int gprhip_problem_create_ex(int device, int cov_kind, int precision, int64_t n,
     if (const char* e = getenv("GPRHIP_POTRF_CHAIN")) p->potrf_chain_mode = atoi(e);
     if (const char* e = getenv("GPRHIP_COV_OVERLAP")) p->cov_overlap = atoi(e);
 #endif
-    GPR_HIP(hipStreamCreate(&p->stream));
+    if (share) p->stream = share->parent->stream;
+    else GPR_HIP(hipStreamCreate(&p->stream));
     GPR_HIP(hipStreamCreate(&p->stream2));
     for (int k = 0; k < 2; ++k) {
       GPR_HIP(hipEventCreateWithFlags(&p->ev_cov[k], hipEventDisableTiming));
@@ -2362,16 +2622,26 @@ int gprhip_problem_create_ex(int device, int cov_kind, int precision, int64_t n,
     const int mp = p->mp;
     const int64_t mm = (int64_t)mp * mp;
     const int64_t npad = (int64_t)p->nchunks * chunk;
-    p->X = p->alloc<double>(n * D);
-    p->y = p->alloc<double>(npad);
+    if (share) {
+      p->X = share->parent->X;
+      p->y = share->parent->y;
+    } else {
+      p->X = p->alloc<double>(n * D);
+      p->y = p->alloc<double>(npad);
+    }
     if (cov_kind == GPRHIP_COV_SE_FAT) p->P = p->alloc<double>(n * d);
     {  // the per-evaluation parameter block and its pinned host mirror (upload_hypers)
       const bool fat = cov_kind == GPRHIP_COV_SE_FAT;
       const int64_t o_shift = (int64_t)mp * d, o_tproj = o_shift + 64, o_het = o_tproj + (fat ? round_up((int64_t)D * d, 2) : 0),
                     o_ms = o_het + (fat ? mp : 0);
       p->hy_len = o_ms + (fat ? (int64_t)mp * d : 0);
-      p->hy_dev = p->alloc<double>(p->hy_len);
-      GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->hy_host), (size_t)p->hy_len * sizeof(double), hipHostMallocDefault));
+      if (share) {
+        p->hy_dev = share->hy_dev;
+        p->hy_host = share->hy_host;
+      } else {
+        p->hy_dev = p->alloc<double>(p->hy_len);
+        GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->hy_host), (size_t)p->hy_len * sizeof(double), hipHostMallocDefault));
+      }
       GPR_HIP(hipEventCreateWithFlags(&p->ev_hy, hipEventDisableTiming));
       p->Z = p->hy_dev; p->hZ = p->hy_host;
       p->zshift = p->hy_dev + o_shift; p->hShift = p->hy_host + o_shift;
@@ -2437,7 +2707,7 @@ int gprhip_problem_create_ex(int device, int cov_kind, int precision, int64_t n,
         fprintf(stderr, "gprhip: device %d: allocated %.3f GB at creation, %.3f GB planned without the V store\n", device,
                 p->alloc_bytes / 1e9, (plan.total - plan.v_store) / 1e9);
     }
-    GPR_HIP(hipMemsetAsync(p->y, 0, (size_t)npad * sizeof(double), p->stream));
+    if (!share) GPR_HIP(hipMemsetAsync(p->y, 0, (size_t)npad * sizeof(double), p->stream));
     // R^-1 is written on its upper tiles only; the fp32 conversion reads the whole square
     GPR_HIP(hipMemsetAsync(p->rfinv, 0, (size_t)mm * sizeof(double), p->stream));
     GPR_HIP(hipStreamSynchronize(p->stream));
@@ -2449,14 +2719,15 @@ void gprhip_problem_destroy(gprhip_problem* p) {
   hipSetDevice(p->device);
   if (p->stream) {
     hipStreamSynchronize(p->stream);
-    hipStreamDestroy(p->stream);
+    if (!p->is_lane) hipStreamDestroy(p->stream);
   }
+  batch_orphan_all(p);  // batches that borrow this problem lose their inputs, targets and stream: they can only be destroyed
   if (p->stream2) {
     hipStreamSynchronize(p->stream2);
     hipStreamDestroy(p->stream2);
   }
   if (p->ev_hy) hipEventDestroy(p->ev_hy);
-  if (p->hy_host) hipHostFree(p->hy_host);
+  if (p->hy_host && !p->is_lane) hipHostFree(p->hy_host);
   if (p->res_host) hipHostFree(p->res_host);
   if (p->ev_fork) hipEventDestroy(p->ev_fork);
   if (p->ev_join) hipEventDestroy(p->ev_join);
@@ -2539,6 +2810,107 @@ int gprhip_set_targets_device(gprhip_problem* p, const double* d_targets) {
     GPR_HIP(hipStreamSynchronize(p->stream));
     p->have_targets = true;
   });
+}
+
+int gprhip_batch_create(gprhip_problem* p, int lanes, gprhip_batch** out) {
+  return guarded([&] {
+    if (out) *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+      (void)hipGetLastError();
+      set_error("gprhip_batch_create: no HIP device is visible");
+      throw HipFail{ST_HIP_ERROR};
+    }
+    if (!p || !out || p->is_lane || lanes < 1 || lanes > GPRHIP_MAX_BATCH) {
+      set_error("gprhip_batch_create: invalid arguments (need a problem and 1 <= lanes <= GPRHIP_MAX_BATCH)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (p->f32 || !p->small_path || p->engine_steps || !small_path_fits(p->m, p->mp, p->d, 0, p->n, false)) {
+      set_error("gprhip_batch_create: batches run the small path only (fp64, at most 64 inducing points of at most 16 "
+                "dimensions, GPRHIP_SMALL_PATH not 0): evaluate this problem with gprhip_eval");
+      throw HipFail{ST_BAD_ARG};
+    }
+    GPR_HIP(hipSetDevice(p->device));
+    auto* b = new gprhip_batch();
+    try {
+      // a lane's slice of the upload block: its parameter block, then one struct per launch, each on a 16-byte boundary
+      int64_t off = round_up(hy_block_len(p->kind, p->mp, p->D, p->d) * (int64_t)sizeof(double), 16);
+      auto place = [&](int64_t& o, size_t bytes) {
+        o = off;
+        off += round_up((int64_t)bytes, 16);
+      };
+      place(b->o_km, sizeof(PotrfKmLane)); place(b->o_p1, sizeof(SmallPass1Args)); place(b->o_r1, sizeof(SmallReduce1Args));
+      place(b->o_fuse, sizeof(PotrfFuseLane)); place(b->o_p2, sizeof(SmallPass2Args)); place(b->o_r2, sizeof(SmallReduce2Args));
+      place(b->o_fin, sizeof(SmallFinishArgs)); place(b->o_ship, sizeof(ShipArgs));
+      b->stride = round_up(off, 64);
+      {  // all lanes against what the device has free, before the first allocation
+        const int64_t need = lanes * (batch_lane_bytes(p) + b->stride);
+        size_t free_b = 0, total_b = 0;
+        GPR_HIP(hipMemGetInfo(&free_b, &total_b));
+        if ((uint64_t)need > (uint64_t)free_b) {
+          char buf[256];
+          snprintf(buf, sizeof buf, "gprhip_batch_create: %d lanes need %.2f GB on device %d (%.1f MB each) and %.2f GB are free "
+                   "of %.2f GB", lanes, need / 1e9, p->device, need / 1e6 / lanes, free_b / 1e9, total_b / 1e9);
+          set_error(buf);
+          throw HipFail{ST_OOM};
+        }
+      }
+      GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->up_host), (size_t)(b->stride * lanes), hipHostMallocDefault));
+      std::memset(b->up_host, 0, (size_t)(b->stride * lanes));
+      GPR_HIP(hipMalloc(reinterpret_cast<void**>(&b->up_dev), (size_t)(b->stride * lanes)));
+      for (int j = 0; j < lanes; ++j) {
+        LaneShare sh{p, reinterpret_cast<double*>(b->up_dev + j * b->stride), reinterpret_cast<double*>(b->up_host + j * b->stride)};
+        gprhip_problem* l = nullptr;
+        const int st = problem_create_impl(p->device, p->kind, GPRHIP_F64, p->n, p->D, p->d, p->m, p->chunk, &l, &sh);
+        if (l) b->lanes.push_back(l);
+        if (st != GPRHIP_OK) throw HipFail{st};
+        // what an evaluation would otherwise allocate when it first runs (ensure_eval_scratch): nothing is left for later
+        l->Vstore = l->alloc<double>((int64_t)l->nchunks * l->chunk * l->mp);
+        l->small_part = l->alloc<double>(small_part_len(l->d, l->D));
+        if (l->d <= 8) l->small_k = l->alloc<double>(round_up(l->n, TILE) * 64);
+      }
+      GPR_HIP(hipStreamSynchronize(p->stream));
+    } catch (...) {
+      (void)hipGetLastError();
+      const std::string msg = last_error();
+      b->parent = nullptr;
+      gprhip_batch_destroy(b);
+      set_error(msg);
+      throw;
+    }
+    b->parent = p;
+    p->batches.push_back(b);
+    *out = b;
+  });
+}
+
+void gprhip_batch_destroy(gprhip_batch* b) {
+  if (!b) return;
+  if (b->parent) {
+    hipSetDevice(b->parent->device);
+    hipStreamSynchronize(b->parent->stream);
+    auto& v = b->parent->batches;
+    v.erase(std::remove(v.begin(), v.end(), b), v.end());
+  }
+  for (gprhip_problem* l : b->lanes) {
+    if (!b->parent) l->stream = nullptr;
+    gprhip_problem_destroy(l);
+  }
+  if (b->up_host) hipHostFree(b->up_host);
+  if (b->up_dev) hipFree(b->up_dev);
+  delete b;
+}
+
+int gprhip_batch_lanes(const gprhip_batch* b) { return b ? (int)b->lanes.size() : 0; }
+
+gprhip_problem* gprhip_batch_lane(gprhip_batch* b, int j) {
+  return (b && j >= 0 && j < (int)b->lanes.size()) ? b->lanes[j] : nullptr;
+}
+
+int gprhip_batch_eval(gprhip_batch* b, int count, const gprhip_hypers* h, int want_grad, gprhip_result* res, double* grad,
+                      int64_t ldg, double* coeffs, int* status) {
+  gprhip_problem* l0 = (b && !b->lanes.empty()) ? b->lanes[0] : nullptr;
+  return guarded([&] { batch_eval(b, count, h, want_grad, res, grad, ldg, coeffs, status); }, l0);
 }
 
 int64_t gprhip_n_hypers(const gprhip_problem* p, int flags) {

@@ -102,6 +102,29 @@ struct PotrfKm {
   double* km = nullptr;
 };
 void launch_potrf_km(const PotrfKm& g, double* A, double* Xinv, int* info, hipStream_t s);
+// Batched evaluation (gprhip_batch_eval): the two single-block factorisations with one lane per blockIdx.y, each lane's
+// arguments read from a device array (d_lanes, `count` entries) -- the same body, the same numbers as the single launches
+// (the arrays are strided: lane j's struct lies `stride` bytes behind lane j - 1's, so that one lane's parameter block and all
+//  its structs are contiguous in the upload)
+#ifdef __HIPCC__
+template <typename T>
+__device__ __forceinline__ const T& lane_args(const T* lanes, int64_t stride) {
+  return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(lanes) + (int64_t)blockIdx.y * stride);
+}
+#endif
+struct PotrfKmLane {
+  PotrfKm g;
+  double *A = nullptr, *Xinv = nullptr;
+  int* info = nullptr;
+};
+struct PotrfFuseLane {
+  PotrfFuse f;
+  double *A = nullptr, *Xinv = nullptr;
+  int* info = nullptr;
+  int m_real = 0;
+};
+void launch_potrf_km_batch(const PotrfKmLane* d_lanes, int count, int64_t stride, hipStream_t s);
+void launch_potrf_fused_batch(const PotrfFuseLane* d_lanes, int count, int64_t stride, hipStream_t s);
 void launch_zero_strict_lower(double* A, int mp, hipStream_t s);
 void launch_copy_block(const double* src, int64_t lds, double* dst, int64_t ldd, int rows, int cols,
                        hipStream_t s);
@@ -239,6 +262,8 @@ struct ShipArgs {
   int64_t n[3] = {0, 0, 0};
 };
 void launch_ship(const ShipArgs& a, hipStream_t s);
+// one lane per blockIdx.y, arguments from a device array; n_max: the longest block of any lane (sizes the grid)
+void launch_ship_batch(const ShipArgs* d_lanes, int count, int64_t stride, int64_t n_max, hipStream_t s);
 void launch_build_w(const double* binv, const double* t, const double* G, int mp, double* W,
                     hipStream_t s);
 // Trace terms of W against K_m and its derivatives (lib/fitc_gp.ml:956-973, lib/utils.ml:196-220),
@@ -294,6 +319,26 @@ struct SmallFinishArgs {
   double* ex;
 };
 void launch_small_finish(const SmallFinishArgs& a, hipStream_t s);
+// Batched evaluation: `count` lanes of one shape side by side in blockIdx.y, every lane's struct read from a device array.
+// a0 is lane 0's struct (host): it selects the instantiation and the grid in x exactly as the single launchers do, so a
+// lane has the workgroups, the block-to-workgroup assignment and the in-order partial sums of a single evaluation.
+struct SmallReduce1Args {
+  const double* part;
+  int ng, mp;
+  double *tile, *cvec, *tail;
+};
+struct SmallReduce2Args {
+  const double* part;
+  int ng, mp, d, D, ms, col_rows;
+  double *tile, *colblk, *proj, *tail;
+};
+int small_pass1_groups(int rows_p);  // workgroups in x of the pass kernels (the reductions' `ng`)
+int small_pass2_groups(int rows_p);
+void launch_small_pass1_batch(const SmallPass1Args& a0, const SmallPass1Args* d_lanes, const SmallReduce1Args* d_red, int count,
+                              int64_t stride, hipStream_t s);
+void launch_small_pass2_batch(const SmallPass2Args& a0, int col_rows, const SmallPass2Args* d_lanes, const SmallReduce2Args* d_red,
+                              int count, int64_t stride, hipStream_t s);
+void launch_small_finish_batch(const SmallFinishArgs& a0, const SmallFinishArgs* d_lanes, int count, int64_t stride, hipStream_t s);
 // means and / or variances of a chunk of test points in one kernel (same limits, no multiscales)
 struct SmallPredictArgs {
   CovParams cp;

@@ -342,8 +342,109 @@ class Problem:
         _lib.check(self._lib.gprhip_debug_fetch(self._handle(), name.encode(), _f64_ptr(out), out.size))
         return out
 
+    def batch(self, lanes):
+        """A `Batch` of `lanes` lanes on this problem: up to 64 hyper-parameter sets against its resident data in one
+        chain of launches (gprhip_batch_*; small path only: fp64, m <= 64, d <= 16)."""
+        return Batch(self, lanes)
+
     def last_timings(self):
         names = (C.c_char_p * 32)()
         ms = (C.c_float * 32)()
         k = self._lib.gprhip_last_timings(self._handle(), names, ms, 32)
         return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
+class _LaneProblem(Problem):
+    """A lane's problem of a `Batch`, owned by the batch: predictions and diagnostics after a batch evaluation."""
+
+    def __init__(self, batch, handle):
+        parent = batch.problem
+        self._lib = parent._lib
+        self._h = C.c_void_p(handle)
+        self._batch = batch  # (keeps the owner alive)
+        self.cov_kind, self.n, self.D, self.d, self.m = parent.cov_kind, parent.n, parent.D, parent.d, parent.m
+        self.device, self.precision = parent.device, parent.precision
+
+    def _handle(self):
+        if not self._batch.is_open():
+            raise _lib.GprHipError(_lib.ESTATE, "gpr_amd.Batch: the batch has been closed")
+        return self._h
+
+    def close(self):
+        self._h = C.c_void_p()  # owned by the batch
+
+
+class Batch:
+    """Several hyper-parameter sets against one resident data set in one pass (gprhip_batch_create / _eval).
+
+    `eval(hypers_list, want_grad)` takes one dict of `Problem.eval`'s keyword arguments per lane and returns
+    (evaluations, statuses): evaluations[j] is an `Evaluation`, or None where statuses[j] is not OK (a refused
+    factorisation; `last_error` holds the first such message).  `lane(j)` serves predictions from lane j's state."""
+
+    def __init__(self, problem, lanes):
+        self._lib = _lib.load()
+        self.problem = problem
+        self._h = C.c_void_p()
+        _lib.check(self._lib.gprhip_batch_create(problem._handle(), int(lanes), C.byref(self._h)))
+        self.lanes = int(self._lib.gprhip_batch_lanes(self._h))
+        self.last_error = ""
+
+    def is_open(self):
+        return bool(self._h)
+
+    def close(self):
+        if self._h:
+            self._lib.gprhip_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def lane(self, j):
+        if not self._h:
+            raise _lib.GprHipError(_lib.ESTATE, "gpr_amd.Batch: the batch has been closed")
+        h = self._lib.gprhip_batch_lane(self._h, int(j))
+        if not h:
+            raise IndexError("Batch.lane: lane %d of %d" % (j, self.lanes))
+        return _LaneProblem(self, h)
+
+    def eval(self, hypers_list, want_grad=True):
+        if not self._h:
+            raise _lib.GprHipError(_lib.ESTATE, "gpr_amd.Batch: the batch has been closed")
+        p = self.problem
+        count = len(hypers_list)
+        hs = (Hypers * max(count, 1))()
+        keep = []
+        nh = 1
+        for j, kw in enumerate(hypers_list):
+            kw = dict(kw)
+            h, k = p._hypers(kw.pop("log_ell", 0.0), kw.pop("log_sf2"), kw.pop("sigma2"), kw.pop("inducing"),
+                             kw.pop("tproj", None), kw.pop("variational", False), kw.pop("model_only", False),
+                             kw.pop("jitter", CHOLESKY_JITTER), kw.pop("log_hetero_skedasticity", None),
+                             kw.pop("log_multiscales_m05", None), kw.pop("reuse_v", False))
+            if kw:
+                raise TypeError("Batch.eval: unknown hyper-parameter names %s" % sorted(kw))
+            hs[j] = h
+            keep.append(k)
+            nh = max(nh, p.n_hypers(bool(h.tproj), bool(h.log_hetero_skedasticity), bool(h.log_multiscales_m05)))
+        res = (Result * max(count, 1))()
+        grad = np.empty((nh, max(count, 1)), dtype=np.float64, order="F")
+        coeffs = np.empty((p.m, max(count, 1)), dtype=np.float64, order="F")
+        status = (C.c_int * max(count, 1))()
+        _lib.check(self._lib.gprhip_batch_eval(self._h, count, hs, int(want_grad), res, _f64_ptr(grad), nh,
+                                               _f64_ptr(coeffs), status))
+        del keep
+        statuses = [int(status[j]) for j in range(count)]
+        self.last_error = "" if all(s == _lib.OK for s in statuses) else self._lib.gprhip_last_error().decode("utf-8", "replace")
+        evs = []
+        for j in range(count):
+            if statuses[j] != _lib.OK:
+                evs.append(None)
+                continue
+            r = res[j]
+            evs.append(Evaluation(r.l1, r.l2, r.l, r.dl_dsigma2 if want_grad else None,
+                                  grad[:r.n_hypers, j].copy() if want_grad else None, coeffs[:, j].copy()))
+        return evs, statuses

@@ -373,6 +373,53 @@ int gprhip_set_timing(gprhip_problem* p, int level);
 /* Timings of the last evaluation (milliseconds): fills up to `cap` entries of names/ms; returns the count. */
 int gprhip_last_timings(gprhip_problem* p, const char** names, float* ms, int cap);
 
+/* ---- Several hyper-parameter sets against one data set in one pass ---------------------------------------------------
+ * A multi-start optimisation, a scan over sigma2 or a cross-validation over initialisations evaluates many
+ * hyper-parameter sets against the same inputs and targets.  With at most 64 inducing points one evaluation is a chain of
+ * eight short launches that leaves most of the device idle; a batch runs up to GPRHIP_MAX_BATCH such
+ * evaluations ("lanes") through ONE chain of launches, the lanes side by side in the grid, with one upload and one wait.
+ *
+ *   gprhip_batch_create   `lanes` lanes (1 .. GPRHIP_MAX_BATCH) on problem p.  The batch borrows p's resident inputs and
+ *                         targets (no copy: a later gprhip_set_inputs / gprhip_set_targets on p is seen by the next batch
+ *                         evaluation) and p's device and stream; every lane owns its per-evaluation state.  All lane memory,
+ *                         the scratch of the first evaluation included, is compared with the device's free memory before
+ *                         anything is allocated: GPRHIP_EOOM leaves nothing behind.  Only problems the small path can take
+ *                         are accepted -- fp64, m <= 64, d <= 16, GPRHIP_SMALL_PATH not 0: anything else is GPRHIP_EBADARG
+ *                         (such a caller loops over gprhip_eval).  Without a device: GPRHIP_EHIP.
+ *   gprhip_batch_eval     evaluates h[0 .. count) on lanes 0 .. count - 1 (1 <= count <= lanes).  res[j], column j of grad
+ *                         (Fortran n_hypers x count, leading dimension ldg >= n_hypers; ignored when want_grad = 0) and
+ *                         column j of coeffs (Fortran m x count, or NULL) are lane j's results, status[j] its own outcome:
+ *                         GPRHIP_OK or GPRHIP_ENOTPOSDEF.  A refused lane leaves its outputs unspecified and does not
+ *                         disturb the others; gprhip_last_error() then holds the first refused lane's message, in
+ *                         gprhip_eval's wording.  The return value speaks for the call as a whole (arguments, HIP errors).
+ *                         LANE j EQUALS gprhip_eval WITH h[j] ON A PLAIN PROBLEM OF THE SAME SHAPE AND DATA, BIT FOR BIT,
+ *                         for every count and every position j: a lane runs the single evaluation's workgroups, block
+ *                         assignment and in-order partial sums.
+ *                         All lanes of a call share one option shape: tproj, log_hetero_skedasticity and
+ *                         log_multiscales_m05 each given for all or for none, `variational` and `model_only` equal;
+ *                         everything else is per lane.  GPRHIP_EBADARG: count out of range, mixed option shapes, reuse_v in
+ *                         any lane, a negative sigma2, hypers the small path does not take (more than 64 input dimensions
+ *                         in front of a projection, multiscales with d > 8).  GPRHIP_ESTATE: inputs not set, or targets not
+ *                         set with model_only = 0.  Nothing is enqueued in a refused call, and the lanes keep their state.
+ *   gprhip_batch_lane     lane j's problem, owned by the batch: after a batch evaluation gprhip_predict,
+ *                         gprhip_co_variance_coeffs, gprhip_condition, gprhip_train_stats, gprhip_covariances and
+ *                         gprhip_debug_fetch work on it exactly as after gprhip_eval (GPRHIP_ESTATE after a refused
+ *                         factorisation).  Do not evaluate, set data on or destroy a lane's problem.  Lanes count .. lanes - 1
+ *                         of a shorter evaluation keep the state of their last one.
+ *   p itself is not touched: its evaluation and predictor state and the validity of reuse_v survive a batch evaluation.
+ *   gprhip_set_timing(gprhip_batch_lane(b, 0), 2) times the batched stages ("batch_km_chol", "batch_p1", "batch_b_chol",
+ *   "batch_p2", "batch_finish"); gprhip_last_timings on lane 0 reads them.  p's own timings are not disturbed.
+ *   Order of destruction: either.  A batch that outlives its problem can only be destroyed (evaluating it is GPRHIP_ESTATE,
+ *   and its lanes' problems are no longer usable). */
+#define GPRHIP_MAX_BATCH 64
+typedef struct gprhip_batch gprhip_batch;
+int gprhip_batch_create(gprhip_problem* p, int lanes, gprhip_batch** out);
+void gprhip_batch_destroy(gprhip_batch* b);
+int gprhip_batch_lanes(const gprhip_batch* b);
+gprhip_problem* gprhip_batch_lane(gprhip_batch* b, int j);
+int gprhip_batch_eval(gprhip_batch* b, int count, const gprhip_hypers* h, int want_grad, gprhip_result* res, double* grad,
+                      int64_t ldg, double* coeffs, int* status);
+
 const char* gprhip_last_error(void);
 const char* gprhip_version(void);
 

@@ -269,6 +269,48 @@ struct Evaluation {  // everything one device evaluation returns
   bool has_grad = false;
 };
 
+// Several hyper-parameter sets against one problem's resident data in one pass (RAII over gprhip_batch; include/gprhip.h,
+// "Several hyper-parameter sets ..."): eval() takes one gprhip_hypers per lane and returns one Evaluation and one status
+// per lane; lane(j) is lane j's device problem for predictions.  The batch may be destroyed before or after its problem.
+class Batch {
+ public:
+  Batch(Problem& p, int lanes) : m_(p.m) {
+    check(gprhip_batch_create(p.get(), lanes, &b_));
+  }
+  ~Batch() { gprhip_batch_destroy(b_); }
+  Batch(const Batch&) = delete;
+  Batch& operator=(const Batch&) = delete;
+  gprhip_batch* get() const { return b_; }
+  int lanes() const { return gprhip_batch_lanes(b_); }
+  gprhip_problem* lane(int j) const { return gprhip_batch_lane(b_, j); }
+  // status[j] is GPRHIP_OK or GPRHIP_ENOTPOSDEF (that lane's Evaluation is then unspecified); anything else throws
+  std::vector<Evaluation> eval(const std::vector<gprhip_hypers>& h, bool want_grad, std::vector<int>& status) {
+    const int count = (int)h.size();
+    const gprhip_hypers* h0 = count ? &h[0] : nullptr;
+    const int flags = h0 ? (h0->tproj ? 1 : 0) | (h0->log_hetero_skedasticity ? 2 : 0) | (h0->log_multiscales_m05 ? 4 : 0) : 0;
+    const int64_t nh = gprhip_n_hypers(lane(0), flags);  // (a lane's problem has the parent's shape)
+    std::vector<gprhip_result> res(count ? count : 1);
+    std::vector<double> grad((size_t)nh * (count ? count : 1)), coeffs((size_t)m_ * (count ? count : 1));
+    status.assign(count ? count : 1, GPRHIP_OK);
+    check(gprhip_batch_eval(b_, count, h0, want_grad ? 1 : 0, res.data(), grad.data(), nh, coeffs.data(), status.data()));
+    status.resize(count);
+    std::vector<Evaluation> out(count);
+    for (int j = 0; j < count; ++j) {
+      if (status[j] != GPRHIP_OK) continue;
+      Evaluation& e = out[j];
+      e.l1 = res[j].l1; e.l2 = res[j].l2; e.l = res[j].l; e.dl_dsigma2 = res[j].dl_dsigma2;
+      e.has_grad = want_grad;
+      if (want_grad) e.grad.assign(grad.begin() + (size_t)j * nh, grad.begin() + (size_t)j * nh + res[j].n_hypers);
+      e.coeffs.assign(coeffs.begin() + (size_t)j * m_, coeffs.begin() + (size_t)(j + 1) * m_);
+    }
+    return out;
+  }
+
+ private:
+  gprhip_batch* b_ = nullptr;
+  int m_;
+};
+
 struct Evaluation_many {  // gprhip_eval_targets: k target vectors (the columns of an n x k matrix) on one model
   double l1 = 0, l_sum = 0, dl_dsigma2_sum = 0;
   Vec l;        // k values: Trained.calc_log_evidence per target
