@@ -103,6 +103,7 @@ SIGNATURES = {
     "gprhip_n_hypers": (C.c_int64, [_vp, C.c_int]),
     "gprhip_eval": (C.c_int, [_vp, C.POINTER(Hypers), C.c_int, C.POINTER(Result), _dp, _dp]),
     "gprhip_eval_targets": (C.c_int, [_vp, C.POINTER(Hypers), C.c_int, C.POINTER(TargetsResult), _dp, _dp, _dp]),
+    "gprhip_eval_input_grad": (C.c_int, [_vp, C.POINTER(Hypers), C.POINTER(Result), _dp, _dp, _vp, C.c_int64, C.c_int]),
     "gprhip_ar1_len": (C.c_int64, [_vp]),
     "gprhip_ar2_len": (C.c_int64, [_vp]),
     "gprhip_exchange_len": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -262,14 +262,21 @@ struct gprhip_problem {
   double* tg_Tt() const { return tg_T() + (int64_t)mp * TG_LD; }
   double* tg_B() const { return tg_Tt() + (int64_t)mp * TG_LD; }
   double* tg_C() const { return tg_B() + (int64_t)mp * TG_LD; }
+  // gprhip_eval_input_grad: the evaluation in flight also writes dl/d(training inputs) (input_grad.hip), per chunk in pass 2,
+  // to xg_dst (point-major [n][D]); xg_engine: it takes the engine row path although its shape is one of small.hip / mid.hip
+  // (those keep X only for single-chunk problems)
+  bool xgrad = false, xg_engine = false;
+  double* xg_dst = nullptr;
+  double* xg_buf = nullptr;  // the library's own [n][D] destination of host-side callers (allocated at the first such call)
+  double* xg_g = nullptr;    // [chunk][d] dl/d(projected points) of one chunk (projection hypers; allocated at first use)
   bool use_small() const {
-    return !multi && small_path && !f32 && !engine_steps && small_path_fits(m, mp, d, has_proj() ? D : 0, n, has_ms());
+    return !multi && !xg_engine && small_path && !f32 && !engine_steps && small_path_fits(m, mp, d, has_proj() ? D : 0, n, has_ms());
   }
   // one or two 128-column tiles of inducing points that the small path does not take (65 .. 256 of them, or fewer with more
   // input dimensions than small.hip stages): the row passes and the finish stage of mid.hip
   bool use_mid_gram() const { return mid_gram && n <= MID_GRAM_ROWS; }
   bool use_mid() const {
-    return !multi && mid_path && !f32 && !engine_steps && !use_small() && mid_path_fits(m, mp, d, has_proj() ? D : 0, n, has_ms());
+    return !multi && !xg_engine && mid_path && !f32 && !engine_steps && !use_small() && mid_path_fits(m, mp, d, has_proj() ? D : 0, n, has_ms());
   }
   // two tiles whose Gram accumulations go through mid.hip's own launch pair (else: through the engine's launch)
   bool mid_pair() const { return use_mid() && mp > TILE && use_mid_gram(); }
@@ -1152,6 +1159,23 @@ void fill_row_pass2(const gprhip_problem* p, Args& a) {
   a.w = p->w; a.v = p->v; a.es = proj ? p->es : nullptr; a.X = p->nchunks == 1 ? static_cast<double*>(p->bufB) : nullptr;
 }
 
+// gprhip_eval_input_grad: dl/d(training inputs) of one row chunk from its X (input_grad.hip), written to the destination at
+// the chunk's row offset; K: K_nm of the chunk in memory, or null (recomputed)
+void input_grad_chunk(gprhip_problem* p, const double* Xc, const double* K, int64_t base, int64_t rows) {
+  hipStream_t s = p->stream;
+  const bool proj = p->has_proj();
+  tstart(p, "p2_xgrad");
+  InputGradArgs a;
+  a.X = Xc; a.K = K; a.pts = p->pts() + base * p->d; a.Z = p->Z;
+  a.shift = p->d <= 64 ? p->zshift : p->Z;  // (the centroid is kept for 64 dimensions: beyond, the first inducing point)
+  a.rows = (int)rows; a.m = p->m; a.mp = p->mp; a.d = p->d;
+  a.log_sf2 = p->cp.log_sf2; a.inv_ell2_05 = p->cp.inv_ell2_05;
+  a.G = proj ? p->xg_g : p->xg_dst + base * p->D; a.ldg = p->d;
+  launch_input_grad(a, s);
+  if (proj) launch_input_grad_project(p->xg_g, rows, p->d, p->D, p->tproj, p->xg_dst + base * p->D, p->D, s);
+  tstop(p);
+}
+
 // at most 64 inducing points: Q', the row quantities, X~, X, the column sums of E = X .* K and G~ in one kernel (small.hip);
 // B~^-1 is formed by the finish kernel, R^-1 is not needed
 void pass2_small(gprhip_problem* p, const Ex2<double>& ex) {
@@ -1165,6 +1189,7 @@ void pass2_small(gprhip_problem* p, const Ex2<double>& ex) {
   launch_small_pass2(a, (int)p->col_rows(), ex.tiles, ex.col, ex.proj, ex.tail, p->stream);
   p->x_last = a.X;
   tstop(p);
+  if (p->xgrad) input_grad_chunk(p, a.X, nullptr, 0, p->n);
 }
 
 // one or two 128-column tiles: Q', the row quantities, X~, X, E = X .* K with its moments (and, one tile, G~) in one
@@ -1190,6 +1215,7 @@ void pass2_mid(gprhip_problem* p, const Ex2<double>& ex) {
     }
   }
   tstop(p);
+  if (p->xgrad) input_grad_chunk(p, a.X, nullptr, 0, p->n);
   if (p->mp > TILE) gram_over_v<double>(p, 2, p->mid_pair(), ex.tiles, nullptr);
 }
 
@@ -1318,11 +1344,13 @@ void pass2_engine(gprhip_problem* p, const Ex2<double>& ex) {
     // matrix-core version unless multiscales (or > 64 dimensions) need the scalar kernel; GPRHIP_GRAD_SCALAR=1
     // forces the scalar one (parity tests run both)
     int nbx = p->grad_scalar ? 0 : grad_mfma_col_blocks(ga);
+    const TS* Kc = ga.K;  // K_nm of this chunk in memory, if any
     if (p->d > 64 || ga.D > 64) {
       // wide points: K of the chunk is rebuilt into the chunk buffer that does not hold X, and E = X .* K read from memory
       TS* const Kw = (Xc == bufA) ? bufB : bufA;
       cov_chunk<TS>(p, c, Kw);
       launch_grad_wide(ga, static_cast<const TS*>(Kw), s);
+      Kc = Kw;
       nbx = (mp + 255) / 256;
     } else if (nbx > 0) {
       launch_grad_mfma(ga, s);
@@ -1346,6 +1374,8 @@ void pass2_engine(gprhip_problem* p, const Ex2<double>& ex) {
     }
     launch_reduce_rows(p->scalpart, nslabs * nbx, 2, ex.tail + A2_SUME, 1, s);
     tstop(p);
+    if constexpr (std::is_same<TS, double>::value)
+      if (p->xgrad) input_grad_chunk(p, Xc, Kc, base, rows);
   }
   if (derive_inducing) launch_proj_inducing_grad(ex.col, mp, p->d, p->D, p->tproj, s);
   if (side) GPR_HIP(hipStreamWaitEvent(s, p->ev_binv, 0));  // B~^-1 done: the split-K scratch is free again
@@ -3004,6 +3034,79 @@ int gprhip_eval(gprhip_problem* p, const gprhip_hypers* h, int want_grad, gprhip
     }
     do_finish_enqueue(p, p->ar2);
     do_finish_collect(p, res, grad, coeffs);
+  }, p);
+}
+
+int gprhip_eval_input_grad(gprhip_problem* p, const gprhip_hypers* h, gprhip_result* res, double* grad, double* coeffs,
+                           double* dl_dinputs, int64_t ld, int on_device) {
+  return guarded([&] {
+    if (!p || !h || !h->inducing || !res || !grad) {
+      set_error("gprhip_eval_input_grad: NULL argument");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (!dl_dinputs) {
+      set_error("gprhip_eval_input_grad: dl_dinputs is NULL");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (p->f32) {
+      set_error("gprhip_eval_input_grad: the input gradient is evaluated in fp64 only (GPRHIP_F32_BULK problem)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (p->is_lane) {
+      set_error("gprhip_eval_input_grad: not available on a lane of a batch");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (h->log_multiscales_m05) {
+      set_error("gprhip_eval_input_grad: multiscales are not supported (log_multiscales_m05 != NULL)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (on_device ? ld != p->D : ld < p->D) {
+      set_error("gprhip_eval_input_grad: bad ld (need ld == D for a device buffer, ld >= D for a host buffer)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    check_hypers(p, h);
+    if (!p->have_inputs || (!p->have_targets && !h->model_only)) {
+      set_error("gprhip: inputs/targets not set");
+      throw HipFail{ST_STATE};
+    }
+    if (h->reuse_v && !p->have_v) {
+      set_error("gprhip: reuse_v set but this problem holds no V of a previous evaluation");
+      throw HipFail{ST_STATE};
+    }
+    GPR_HIP(hipSetDevice(p->device));
+    // the library's own buffers of this call, after a look at the device's free memory: a refusal leaves the problem as it was
+    const bool proj = p->kind == GPRHIP_COV_SE_FAT && h->tproj != nullptr;
+    const int64_t need_buf = (!on_device && !p->xg_buf) ? p->n * p->D : 0;
+    const int64_t need_g = (proj && !p->xg_g) ? p->chunk * p->d : 0;
+    if (need_buf + need_g > 0) {
+      size_t free_b = 0, total_b = 0;
+      GPR_HIP(hipMemGetInfo(&free_b, &total_b));
+      if ((size_t)(need_buf + need_g) * sizeof(double) + (size_t(64) << 20) > free_b) {
+        set_error("gprhip_eval_input_grad: not enough device memory for the input-gradient buffers");
+        throw HipFail{ST_OOM};
+      }
+      if (need_buf) p->xg_buf = p->alloc<double>(need_buf);
+      if (need_g) p->xg_g = p->alloc<double>(need_g);
+    }
+    p->xgrad = true;
+    p->xg_engine = p->nchunks > 1;
+    p->xg_dst = on_device ? dl_dinputs : p->xg_buf;
+    try {
+      do_pass1<double>(p, h, 1, p->n, p->ar1);
+      do_pass2<double>(p, p->ar1, p->ar2);
+      do_finish_enqueue(p, p->ar2);
+      do_finish_collect(p, res, grad, coeffs);
+      GPR_HIP(hipStreamSynchronize(p->stream));
+      if (!on_device)
+        GPR_HIP(hipMemcpy2D(dl_dinputs, (size_t)ld * sizeof(double), p->xg_buf, (size_t)p->D * sizeof(double),
+                            (size_t)p->D * sizeof(double), (size_t)p->n, hipMemcpyDeviceToHost));
+    } catch (...) {
+      p->xgrad = p->xg_engine = false;
+      p->xg_dst = nullptr;
+      throw;
+    }
+    p->xgrad = p->xg_engine = false;
+    p->xg_dst = nullptr;
   }, p);
 }
 

@@ -245,6 +245,28 @@ void launch_grad_mfma(const GradArgs<TS>& a, hipStream_t s);
 template <typename TS>
 void launch_grad_fused(const GradArgs<TS>& a, hipStream_t s);
 
+// ---- gradient with respect to the training inputs (input_grad.hip): the row-direction twin of the inducing-point sums above.
+// For one row chunk  G[r][k] = inv_ell2 sum_c X_rc K_rc (p_rk - z_ck)  (inv_ell2 = -2 inv_ell2_05), evaluated as
+// (p_rk - s_k) rowsum(E)_r - (E (Z - s))_rk with E = X .* K and the product E (Z - s) on v_mfma_f64_16x16x4_f64.  Sixteen rows
+// belong to one wavefront, which walks the columns in order: no atomics, the same bits every run.
+struct InputGradArgs {
+  const double* X;       // [rows_p][mp]  X of the chunk: rows < rows and columns < round_up(m, 16) are read (they must be
+                         //     addressable; the values in columns >= m are ignored), nothing else is
+  const double* K;       // [rows_p][mp]  K_nm of the chunk (the resident store, or rebuilt), or null: recomputed (d <= 64 only)
+  const double* pts;     // [rows][d]  inputs (iso) or projections (fat) of the chunk
+  const double* Z;       // [mp][d]
+  const double* shift;   // [d] common offset s subtracted from points and inducing points (any point near the data will do:
+                         //     the centroid of the inducing points for d <= 64, the first inducing point beyond)
+  int rows, m, mp, d;
+  double log_sf2, inv_ell2_05;
+  double* G;             // out [rows][ldg], columns < d written
+  int64_t ldg;
+};
+void launch_input_grad(const InputGradArgs& a, hipStream_t s);
+// out[r][b] = sum_k tproj(b, k) G[r][k]  (Cov_se_fat with projection: dl/dx_r = tproj dl/dp_r; tproj as launch_project takes it)
+void launch_input_grad_project(const double* G, int64_t rows, int d, int D, const double* tproj, double* out, int64_t ldo,
+                               hipStream_t s);
+
 // ---- m x m finalisation (finalize.hip)
 // dst (upper tiles) = base + sum_z slices[z]; the diagonal tiles sum the first nslices_diag slices only (0 = nslices;
 // gemm_syrk_diag_slices for the result of a SYRK-shaped engine launch)

@@ -180,6 +180,39 @@ def _run(model, targets, want_grad, owner):
     return ev
 
 
+def _run_input_grad(model, targets, owner):
+    """As _run with want_grad, through Problem.eval_input_grad: returns (evaluation, D x n gradient of the log evidence with
+    respect to the training inputs).  The evaluation is kept by the owner like any gradient evaluation."""
+    inputs = model.inputs
+    prob = inputs.problem
+    kernel = inputs.inducing.kernel
+    if targets is not None:
+        prob.set_targets(targets)
+    sig = (id(kernel), id(inputs.inducing.points))
+    reuse = getattr(prob, "_last_sig", None) == sig
+    prob._last_sig = prob._state_owner = None
+    ev, g = prob.eval_input_grad(sigma2=model.sigma2, inducing=inputs.inducing.points, variational=model.variational,
+                                 model_only=targets is None, jitter=prob._jitter, reuse_v=reuse,
+                                 **prob._spec.eval_args(kernel))
+    prob._last_sig = sig
+    prob._state_owner = owner
+    prob._last_refs = (kernel, inputs.inducing.points)
+    return ev, g
+
+
+def _trained_input_gradient(trained):
+    if isinstance(trained, _TrainedMany):
+        raise TypeError("Trained.calc_input_gradient: one target vector only (not the object of Trained.calc_many)")
+    trained._ev, g = _run_input_grad(trained.model, trained.targets, trained)
+    trained.want_grad = True
+    return g
+
+
+def _model_input_gradient(model):
+    model._ev[True], g = _run_input_grad(model, None, model)
+    return g
+
+
 class _Standalone:
     """Mean_predictor.t / Co_variance_predictor.t built from stored numbers (lib/fitc_gp.ml:377-391, :429-447)
     rather than from a model on the device: the `test` flow of bin/ocaml_gpr.ml:373-413.  The device problem that
@@ -593,7 +626,10 @@ def _make_variant(spec, variational, functor, cov_kind="FITC"):
         Model=SimpleNamespace(
             calc=model_calc, update_sigma2=model_update_sigma2, calc_eval=lambda m: m,
             calc_log_evidence_sigma2=lambda model: model.evaluation(True).dl_dsigma2,  # :1121-1122
-            prepare_hyper=prepare_hyper_model, calc_log_evidence=hyper_lookup),
+            prepare_hyper=prepare_hyper_model, calc_log_evidence=hyper_lookup,
+            # extension beyond the reference's signature: D x n gradient of the model's log evidence with respect to the
+            # training inputs (fp64 problems, no multiscales)
+            calc_input_gradient=_model_input_gradient),
         Trained=SimpleNamespace(
             calc=lambda model, targets: _Trained(model, targets, True),                 # :1158-1181
             calc_eval=lambda t: t,
@@ -601,7 +637,10 @@ def _make_variant(spec, variational, functor, cov_kind="FITC"):
             prepare_hyper=prepare_hyper_trained, calc_log_evidence=hyper_lookup,
             # extension beyond the reference's signature: k target vectors (n x k) on one model in one evaluation.  The
             # object answers the three *_many functions of Eval.Trained below and Deriv.Optim.calc_gradient
-            calc_many=lambda model, targets: _TrainedMany(model, targets, True)),
+            calc_many=lambda model, targets: _TrainedMany(model, targets, True),
+            # extension: D x n gradient of the trained log evidence with respect to the training inputs, in the layout the
+            # inputs were given in (fp64 problems, no multiscales); one more gradient evaluation on the device
+            calc_input_gradient=_trained_input_gradient),
         Test=SimpleNamespace(self_test=self_test),
         Optim=SimpleNamespace(calc_gradient=calc_gradient),
     )

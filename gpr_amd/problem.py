@@ -157,6 +157,34 @@ class Problem:
         return Evaluation(res.l1, res.l2, res.l, res.dl_dsigma2 if want_grad else None,
                           grad[:res.n_hypers] if want_grad else None, coeffs)
 
+    def eval_input_grad(self, *, log_sf2, sigma2, inducing, log_ell=0.0, tproj=None, variational=False,
+                        model_only=False, jitter=CHOLESKY_JITTER, log_hetero_skedasticity=None,
+                        log_multiscales_m05=None, reuse_v=False, out_device_ptr=None, ld=None):
+        """A gradient evaluation (keyword arguments as `eval`) that also returns dl/d(training inputs): (Evaluation,
+        D x n array in the layout of `set_inputs`).  out_device_ptr: device address of a contiguous point-major [n][D] fp64
+        array (the layout of `set_inputs_device`, e.g. tensor.data_ptr()) that receives it instead -- the second value is
+        then None.  ld (host output only): leading dimension >= D of the returned array's buffer; rows D.. of it are not
+        written (they hold NaN).  fp64 problems, no multiscales (the library refuses otherwise)."""
+        h, keep = self._hypers(log_ell, log_sf2, sigma2, inducing, tproj, variational, model_only, jitter,
+                               log_hetero_skedasticity, log_multiscales_m05, reuse_v)
+        res = Result()
+        nh = self.n_hypers(tproj is not None, log_hetero_skedasticity is not None, log_multiscales_m05 is not None)
+        grad = np.empty(nh, dtype=np.float64)
+        coeffs = np.empty(self.m, dtype=np.float64)
+        if out_device_ptr is not None:
+            out, ptr, ldv, dev = None, C.c_void_p(int(out_device_ptr)), self.D, 1
+        else:
+            ldv = self.D if ld is None else int(ld)
+            out = np.full((max(ldv, 1), self.n), np.nan, dtype=np.float64, order="F")
+            ptr, dev = C.c_void_p(out.ctypes.data), 0
+        _lib.check(self._lib.gprhip_eval_input_grad(self._handle(), C.byref(h), C.byref(res), _f64_ptr(grad), _f64_ptr(coeffs),
+                                                    ptr, ldv, dev))
+        del keep
+        ev = Evaluation(res.l1, res.l2, res.l, res.dl_dsigma2, grad[:res.n_hypers], coeffs)
+        if out is None:
+            return ev, None
+        return ev, (out if ld is not None else out[:self.D])
+
     def eval_targets(self, *, log_sf2, sigma2, inducing, log_ell=0.0, tproj=None, variational=False,
                      model_only=False, want_grad=True, jitter=CHOLESKY_JITTER, log_hetero_skedasticity=None,
                      log_multiscales_m05=None, reuse_v=False):

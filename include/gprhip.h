@@ -195,6 +195,33 @@ int gprhip_eval(gprhip_problem* p, const gprhip_hypers* h, int want_grad, gprhip
 int gprhip_eval_targets(gprhip_problem* p, const gprhip_hypers* h, int want_grad, gprhip_targets_result* res, double* l2,
                         double* grad_sum, double* coeffs);
 
+/* ---- Gradient with respect to the training inputs -------------------------------------------------------------------
+ * A gradient evaluation (want_grad = 1 semantics: res, grad, coeffs exactly as gprhip_eval returns them) that also returns
+ * dl/dx for every training input -- what a caller needs when the inputs are themselves the output of something trainable
+ * (a feature extractor in front of the GP, a learned input warping, latent inputs).  For the squared-exponential kernels
+ * diag K_n and K_m do not depend on the training inputs: with E = X .* K_nm and p_r the point the kernel sees,
+ *   dl/dp_rk = inv_ell2 sum_c E_rc (p_rk - z_ck),   dl/dx_r = tproj dl/dp_r   (Cov_se_fat with a projection)
+ * evaluated per row chunk in pass 2 (stage timer "p2_xgrad").  For a model-only evaluation it is dl1/dx.
+ *   on_device = 0: dl_dinputs is a host buffer, Fortran D x n, ld >= D (the layout of gprhip_set_inputs; rows D..ld-1 of
+ *                  every column are left untouched).  The library keeps an n x D device buffer for it, allocated at the
+ *                  first such call after a comparison with the device's free memory: GPRHIP_EOOM leaves the problem as
+ *                  it was.
+ *   on_device = 1: dl_dinputs is a device pointer, point-major [n][D], ld == D (the layout of gprhip_set_inputs_device),
+ *                  written directly; complete when the call returns.
+ * Limits: fp64 and one device only.  GPRHIP_EBADARG for a GPRHIP_F32_BULK problem, for log_multiscales_m05 != NULL (the
+ * multiscale exponent needs per-column weights), for dl_dinputs == NULL and for a bad ld.  reuse_v, variational,
+ * model_only, tproj and log_hetero_skedasticity are honoured; GPRHIP_ESTATE applies as for the plain evaluation.  A refused
+ * call enqueues nothing and leaves the problem's state valid; after a completed one the problem serves predictions etc.
+ * exactly as after the plain evaluation.
+ * Row path: a single-chunk problem keeps its path, and res, grad and coeffs then equal the plain evaluation's bit for bit.
+ * A shape of the one-kernel row passes (at most 256 inducing points) held in SEVERAL chunks takes the engine row path for
+ * this call -- those passes keep X only for single-chunk problems -- so there res, grad and coeffs agree with the plain
+ * evaluation to rounding only.
+ * The plain, the several-target, the batched, the staged and the sharded evaluations are untouched and do not take this
+ * output. */
+int gprhip_eval_input_grad(gprhip_problem* p, const gprhip_hypers* h, gprhip_result* res, double* grad, double* coeffs,
+                           double* dl_dinputs, int64_t ld, int on_device);
+
 /* Staged form for row-sharded evaluation across devices (one process per device).  Between the
  * stages the caller sums the exchange buffers over all shards (RCCL all-reduce on the same HIP
  * stream or after a stream sync -- the buffers are plain device memory owned by the caller):

@@ -402,6 +402,38 @@ struct Make_deriv {
     return ev;
   }
 
+  // A gradient evaluation that also returns the D x n gradient of the log evidence with respect to the training inputs
+  // (gprhip_eval_input_grad: an extension beyond the reference's signature; fp64 problems, no multiscales) -- what
+  // gpr_amd/fitc_gp.py calls Deriv.Trained.calc_input_gradient (targets given) / Deriv.Model.calc_input_gradient (null).
+  // `owner` as in run.
+  static Evaluation run_input_grad(const Model_t& model, const Vec* targets, Mat& dl_dinputs, std::shared_ptr<const void> owner) {
+    Problem& prob = *model.inputs.problem;
+    const Kernel& k = model.inputs.inducing.kernel;
+    const Mat& z = *model.inputs.inducing.points;
+    if (targets) check(gprhip_set_targets(prob.get(), targets->data()));
+    gprhip_hypers h{};
+    Spec::fill(k, h);
+    h.sigma2 = model.sigma2;
+    h.inducing = z.data();
+    h.variational = model.variational;
+    h.model_only = targets ? 0 : 1;
+    h.jitter = cholesky_jitter;
+    h.reuse_v = (prob.last_kernel == model.kernel_ref && prob.last_inducing == model.inputs.inducing.points);
+    Evaluation ev;
+    ev.grad.assign((size_t)std::max<int64_t>(1, gprhip_n_hypers(prob.get(), Spec::flags(k))), 0.0);
+    ev.coeffs.assign((size_t)prob.m, 0.0);
+    dl_dinputs = Mat(prob.D, (int)prob.n);
+    gprhip_result r{};
+    check(gprhip_eval_input_grad(prob.get(), &h, &r, ev.grad.data(), ev.coeffs.data(), dl_dinputs.data(), prob.D, 0));
+    ev.l1 = r.l1; ev.l2 = r.l2; ev.l = r.l; ev.dl_dsigma2 = r.dl_dsigma2;
+    ev.has_grad = true;
+    ev.grad.resize((size_t)r.n_hypers);
+    prob.last_kernel = model.kernel_ref;
+    prob.last_inducing = model.inputs.inducing.points;
+    prob.state_owner = std::move(owner);
+    return ev;
+  }
+
   // Several target vectors on one model in one device evaluation (an extension beyond the reference's signature, whose
   // Trained.t holds one target vector); the Variational flag travels in the model, so the two helpers serve every variant
   // (what gpr_amd/fitc_gp.py calls Trained.calc_many).  `owner` as in run.
