@@ -49,6 +49,8 @@ external eval : problem -> hypers -> bool -> vec -> vec -> float * float * float
 (* want_grad grad coeffs -> (l1, l2, l, dl_dsigma2, n_hypers) *)
 external n_hypers : problem -> int -> int = "gprhip_ml_n_hypers"
 external predict : problem -> mat -> bool -> vec -> vec option -> unit = "gprhip_ml_predict"
+(* gradients of the predictive means / variances with respect to the test inputs (D x nt each; either may be None) *)
+external predict_input_grad : problem -> mat -> mat option -> mat option -> unit = "gprhip_ml_predict_input_grad"
 external train_stats : problem -> vec option -> vec -> unit = "gprhip_ml_train_stats"
 external covariances : problem -> mat -> int -> bool -> mat -> unit = "gprhip_ml_covariances"
 external cov_samples : problem -> mat -> float -> float -> vec -> mat -> mat -> unit
@@ -515,6 +517,20 @@ module Make_variant
         | Mean_predictor.Stored s -> predict (load_stored inputs ~sigma2:0. ~coeffs:s.coeffs ()) inputs.Inputs.points false means None);
         { points = inputs.Inputs.points; means }
 
+      (* D x nt: the gradient of the means with respect to the test inputs (an extension beyond the reference's implemented
+         surface, which only names calc_mpi_deriv in Sigs.Optimizer); one device serves it: the state is replicated *)
+      let calc_input_gradient mean_predictor (inputs : Inputs.t) =
+        same_inducing (Mean_predictor.get_inducing mean_predictor) inputs.Inputs.inducing.Inducing.points
+          "Means.calc_input_gradient";
+        let g = Mat.create (Mat.dim1 inputs.Inputs.points) (Spec.Inputs.get_n_points inputs.Inputs.points) in
+        (match mean_predictor with
+        | Mean_predictor.Of_trained trained ->
+            Trained.ensure_state trained;
+            predict_input_grad (Lazy.force trained.Trained.model.Model.inputs.Inputs.dev).first inputs.Inputs.points (Some g) None
+        | Mean_predictor.Stored s ->
+            predict_input_grad (load_stored inputs ~sigma2:0. ~coeffs:s.coeffs ()) inputs.Inputs.points (Some g) None);
+        g
+
       let get t = t.means
     end
 
@@ -541,6 +557,20 @@ module Make_variant
             same_inducing s.inducing inputs.Inputs.inducing.Inducing.points "Variances.calc";
             predict (load_stored inputs ~sigma2 ~factors:s.coeffs ()) inputs.Inputs.points false means (Some variances));
         { points = inputs.Inputs.points; variances; sigma2 }
+
+      (* D x nt: the gradient of the variances with respect to the test inputs (the same for predictive and latent ones) *)
+      let calc_input_gradient co_variance_predictor ~sigma2 (inputs : Inputs.t) =
+        let g = Mat.create (Mat.dim1 inputs.Inputs.points) (Spec.Inputs.get_n_points inputs.Inputs.points) in
+        (match co_variance_predictor with
+        | Co_variance_predictor.Of_model model ->
+            same_inducing model.Model.inputs.Inputs.inducing.Inducing.points inputs.Inputs.inducing.Inducing.points
+              "Variances.calc_input_gradient";
+            Model.ensure_state model;
+            predict_input_grad (Lazy.force model.Model.inputs.Inputs.dev).first inputs.Inputs.points None (Some g)
+        | Co_variance_predictor.Stored s ->
+            same_inducing s.inducing inputs.Inputs.inducing.Inducing.points "Variances.calc_input_gradient";
+            predict_input_grad (load_stored inputs ~sigma2 ~factors:s.coeffs ()) inputs.Inputs.points None (Some g));
+        g
 
       (* lib/fitc_gp.ml:487-496: at the model's own inputs the same numbers Variances.calc gives there *)
       let calc_model_inputs (model : Model.t) =

@@ -144,6 +144,24 @@ CAMLprim value gprhip_ml_predict(value prob, value points, value predictive, val
   CAMLreturn(Val_unit);
 }
 
+/* external predict_input_grad : problem -> mat -> dmeans:mat option -> dvariances:mat option -> unit
+ *   gradients of the predictive means / variances with respect to the test inputs (D x nt, the layout of the points) */
+CAMLprim value gprhip_ml_predict_input_grad(value prob, value points, value dmeans, value dvariances) {
+  CAMLparam4(prob, points, dmeans, dvariances);
+  struct caml_ba_array* ba = Caml_ba_array_val(points);
+  gprhip_problem* p = Problem_val(prob);
+  const double* x = (const double*)ba->data;
+  int64_t ld = ba->dim[0], nt = ba->dim[1];
+  double* dm = (double*)opt_data(dmeans);
+  double* dv = (double*)opt_data(dvariances);
+  int status;
+  caml_release_runtime_system();
+  status = gprhip_predict_input_grad(p, x, ld, nt, 0, NULL, NULL, dm, dv, ld, 0);
+  caml_acquire_runtime_system();
+  check(status);
+  CAMLreturn(Val_unit);
+}
+
 /* external train_stats : problem -> means:vec option -> sums:vec -> unit      sums = [sse; sum|e|; max|e|; sum y^2] */
 CAMLprim value gprhip_ml_train_stats(value prob, value means, value sums) {
   CAMLparam3(prob, means, sums);

@@ -115,6 +115,7 @@ SIGNATURES = {
     "gprhip_stream": (_vp, [_vp]),
     "gprhip_set_timing": (C.c_int, [_vp, C.c_int]),
     "gprhip_predict": (C.c_int, [_vp, _dp, C.c_int64, C.c_int64, C.c_int, _dp, _dp]),
+    "gprhip_predict_input_grad": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, _vp, _vp, _vp, _vp, C.c_int64, C.c_int]),
     "gprhip_predict_targets": (C.c_int, [_vp, _dp, C.c_int64, C.c_int64, _dp]),
     "gprhip_train_stats": (C.c_int, [_vp, _dp, _dp]),
     "gprhip_covariances": (C.c_int, [_vp, _dp, C.c_int64, C.c_int64, C.c_int, C.c_int, _dp]),

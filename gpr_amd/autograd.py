@@ -7,7 +7,11 @@ the hyper-parameters, evaluated by the HIP library on the tensors' own device me
 `inputs` may be the output of anything trainable (a feature extractor in front of the GP, an input warping, latent inputs):
 its gradient is written by the library straight into a fresh tensor (gprhip_eval_input_grad, on_device = 1).
 
-torch is imported when `log_evidence` is first called, not with this module: `import gpr_amd` never starts importing it.
+`predict(problem, test_inputs)` is the posterior side: predictive mean and variance as differentiable functions of the test
+inputs (gprhip_predict_input_grad, on_device = 1) -- an acquisition function over candidate points, an input uncertainty pushed
+through the model, a feature extractor in front of the GP at prediction time.
+
+torch is imported when `log_evidence` or `predict` is first called, not with this module: `import gpr_amd` never starts importing it.
 """
 from __future__ import annotations
 
@@ -113,3 +117,59 @@ def log_evidence(problem, inputs, targets, *, log_sf2, log_sigma2, inducing, log
         return v if (v is None or isinstance(v, torch.Tensor)) else torch.tensor(float(v), dtype=torch.float64)
     return _function().apply(problem, bool(variational), inputs, targets, as_t(log_sf2), as_t(log_sigma2), inducing,
                              as_t(log_ell), tproj)
+
+
+_predict_fn = None
+
+
+def _predict_function():
+    """The torch.autograd.Function of `predict`, made at first use."""
+    global _predict_fn
+    if _predict_fn is not None:
+        return _predict_fn
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class _Predict(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, problem, predictive, x):
+            D = problem.D
+            if x.dtype != torch.float64 or x.dim() != 2 or x.shape[1] != D or not x.is_contiguous() or not x.is_cuda:
+                raise ValueError("predict: test_inputs must be a contiguous (nt, %d) float64 tensor on the problem's device" % D)
+            if x.device.index != problem.device:
+                raise ValueError("predict: test_inputs live on device %s, the problem on device %d"
+                                 % (x.device.index, problem.device))
+            nt = int(x.shape[0])
+            mean = torch.empty(nt, dtype=torch.float64, device=x.device)
+            var = torch.empty(nt, dtype=torch.float64, device=x.device)
+            ptrs = {"means": mean.data_ptr(), "variances": var.data_ptr()}
+            need = ctx.needs_input_grad[2]
+            if need:
+                dm = torch.empty((nt, D), dtype=torch.float64, device=x.device)
+                dv = torch.empty((nt, D), dtype=torch.float64, device=x.device)
+                ptrs.update(dmeans=dm.data_ptr(), dvariances=dv.data_ptr())
+                ctx.grads = (dm, dv)
+            # the library works on its own stream: what produced the tensor must be complete before it reads it (its own
+            # outputs are complete when the call returns)
+            torch.cuda.current_stream(x.device).synchronize()
+            problem.predict_input_grad(x.data_ptr(), predictive=predictive, want=tuple(ptrs), out_device_ptrs=ptrs, nt=nt)
+            return mean, var
+
+        @staticmethod
+        @once_differentiable  # (the stored gradients are numbers, not a graph: a second derivative raises instead of being zero)
+        def backward(ctx, g_mean, g_var):
+            if not ctx.needs_input_grad[2]:
+                return None, None, None
+            dm, dv = ctx.grads
+            return None, None, g_mean[:, None] * dm + g_var[:, None] * dv
+
+    _predict_fn = _Predict
+    return _predict_fn
+
+
+def predict(problem, test_inputs, predictive=True):
+    """(mean, var): the predictive means and variances of `problem`'s current model state (a gpr_amd.Problem, fp64, after an
+    evaluation or `load_predictor`) at `test_inputs`, an (nt, D) contiguous float64 tensor on the problem's device, as (nt,)
+    float64 tensors.  One library call runs in forward; backward returns g_mean[:, None] * dmeans + g_var[:, None] * dvariances.
+    predictive=True adds sigma2 to the variances (not to the gradients)."""
+    return _predict_function().apply(problem, bool(predictive), test_inputs)

@@ -269,6 +269,13 @@ struct gprhip_problem {
   double* xg_dst = nullptr;
   double* xg_buf = nullptr;  // the library's own [n][D] destination of host-side callers (allocated at the first such call)
   double* xg_g = nullptr;    // [chunk][d] dl/d(projected points) of one chunk (projection hypers; allocated at first use)
+  // gprhip_predict_input_grad: M = U^-1 (I - R~^-1 R~^-T) U^-T (mp x mp, full) of the current model state -- formed at the
+  // first call that asks for a variance part, kept until an evaluation or gprhip_load_predictor clears pg_m_valid
+  double* pg_m = nullptr;
+  bool pg_m_valid = false;
+  double* pg_buf = nullptr;  // gradient staging of one chunk: [2][rows][D] for a host destination + [2][rows][d] dp (projection)
+  int64_t pg_rows = 0;       // rows it holds
+  bool pg_host = false, pg_proj = false;  // ... with those two parts
   bool use_small() const {
     return !multi && !xg_engine && small_path && !f32 && !engine_steps && small_path_fits(m, mp, d, has_proj() ? D : 0, n, has_ms());
   }
@@ -1088,6 +1095,7 @@ void do_pass1(gprhip_problem* p, const gprhip_hypers* h, int want_grad, int64_t 
   p->stage = 0;
   p->x_last = nullptr;
   p->cond_km = -1.0;
+  p->pg_m_valid = false;
   upload_hypers(p, h);
   p->want_grad = want_grad;
   p->n_total = n_total;
@@ -1727,6 +1735,7 @@ void batch_stage_lane(gprhip_batch* b, int j, const gprhip_hypers* h, int want_g
   l->tg_coeffs = false;
   l->x_last = nullptr;
   l->cond_km = -1.0;
+  l->pg_m_valid = false;
   l->have_v = l->have_k = l->small_k_valid = false;
   stage_hypers(l, h);
   l->want_grad = want_grad;
@@ -1970,6 +1979,189 @@ void do_predict(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_
     }
     GPR_HIP(hipStreamSynchronize(s));  // xt / row buffers are reused by the next chunk
   }
+}
+
+// gprhip_predict_input_grad: M = U^-1 (I - R~^-1 R~^-T) U^-T of the current model state (full symmetric), with the m x m
+// machinery of the finish stage.  I - B~^-1 has its spectrum in [0, 1): in this whitened form M carries no cancellation of
+// (K_m + jitter)^-1 against B^-1 beyond what the variance itself has.  binv, wtil and kj are scratch between evaluations.
+void ensure_predict_m(gprhip_problem* p) {
+  if (p->pg_m_valid) return;
+  hipStream_t s = p->stream;
+  const int mp = p->mp;
+  tstart(p, "pg_m");
+  triu_xxt(p, p->rinv, p->binv, s);  // B~^-1 = R~^-1 R~^-T (upper tiles; identity on the padding)
+  launch_identity_minus_sym(p->binv, mp, p->wtil, s);
+  const int ks = ((int64_t)(mp / TILE) * (mp / TILE) <= 256) ? mxm_slices(mp) : 1;
+  GemmArgs y;  // Y = (I - B~^-1) U^-T
+  y.A = p->wtil; y.lda = mp; y.B = p->uinv; y.ldb = mp; y.C = p->kj; y.ldc = mp;
+  y.M = mp; y.N = mp; y.K = mp; y.tri = TRI_KLO_BN;
+  gemm_splitk(p, OP_NT, y, ks);
+  GemmArgs w;  // M = U^-1 Y
+  w.A = p->uinv; w.lda = mp; w.B = p->kj; w.ldb = mp; w.C = p->pg_m; w.ldc = mp;
+  w.M = mp; w.N = mp; w.K = mp; w.tri = TRI_KLO_BM;
+  gemm_splitk(p, OP_NN, w, ks);
+  tstop(p);
+  p->pg_m_valid = true;
+}
+
+// Means / variances of do_predict and their gradients with respect to the test inputs (predict_grad.hip), chunk by chunk with
+// do_predict's buffers and chunk rule.  The caller has checked the arguments and the limits.
+void do_predict_input_grad(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_t nt, int predictive, double* means,
+                           double* variances, double* dmeans, double* dvariances, int64_t ldg, int on_device) {
+  const bool want_mean = means || dmeans, want_var = variances || dvariances;
+  if (!p->have_model || p->stage != 0) {
+    set_error("gprhip_predict_input_grad: no completed evaluation to predict from");
+    throw HipFail{ST_STATE};
+  }
+  if (p->has_ms()) {
+    set_error("gprhip_predict_input_grad: multiscales are not supported (the model state has log_multiscales_m05)");
+    throw HipFail{ST_BAD_ARG};
+  }
+  if (want_var && !p->have_factors) {
+    set_error("gprhip_predict_input_grad: the loaded predictor has no co-variance coefficients (chol_km, r_mat)");
+    throw HipFail{ST_STATE};
+  }
+  if (want_mean && p->multi_state) {
+    set_error("gprhip_predict_input_grad: the last evaluation was gprhip_eval_targets (several target vectors): means and "
+              "their gradients are available after the next gprhip_eval");
+    throw HipFail{ST_STATE};
+  }
+  if (want_mean) need_trustworthy_coeffs(p, "gprhip_predict_input_grad");
+  GPR_HIP(hipSetDevice(p->device));
+  hipStream_t s = p->stream;
+  const int mp = p->mp, D = p->D, d = p->d;
+  const bool proj = p->has_proj();
+  const bool small = p->small_path && p->m <= 64 && mp == TILE && d <= 16;
+  const bool mats = !small && want_var;  // K and G of a chunk are matrices in memory
+  // the chunk rule of do_predict
+  int64_t chunk = p->chunk;
+  const int64_t want = std::min<int64_t>(131072, round_up(nt, TILE));
+  bool grow_pred = false;
+  if (want > chunk) {
+    const int64_t rows = std::min<int64_t>(131072, std::max(want, 8 * chunk));
+    if (mats) {
+      grow_pred = p->pred_rows < want;
+      chunk = grow_pred ? rows : p->pred_rows;
+    } else {
+      chunk = std::max(p->xt_rows >= want ? p->xt_rows : rows, p->chunk);
+    }
+  }
+  // everything this call allocates, after a look at the device's free memory: a refusal leaves the problem as it was
+  const bool host_g = !on_device && (dmeans || dvariances);
+  const bool need_m = mats && !p->pg_m;
+  const bool grow_xt = !(p->xt && p->xt_rows >= chunk);
+  const bool grow_pg = (host_g || proj) && (p->pg_rows < chunk || (host_g && !p->pg_host) || (proj && !p->pg_proj));
+  const bool pg_host = host_g || p->pg_host, pg_proj = proj || p->pg_proj;
+  const int64_t pg_len = 2 * chunk * ((pg_host ? D : 0) + (pg_proj ? d : 0));
+  {
+    int64_t need = 0;
+    if (need_m) need += (int64_t)mp * mp * 8;
+    if (grow_pred) need += 2 * chunk * mp * 8;
+    if (grow_xt) need += chunk * (D + d + 3) * 8;
+    if (grow_pg) need += pg_len * 8;
+    if (need > 0) {
+      size_t free_b = 0, total_b = 0;
+      GPR_HIP(hipMemGetInfo(&free_b, &total_b));
+      if ((size_t)need + (size_t(64) << 20) > free_b) {
+        set_error("gprhip_predict_input_grad: not enough device memory for M and the chunk buffers of the prediction gradient");
+        throw HipFail{ST_OOM};
+      }
+    }
+  }
+  if (need_m) p->pg_m = p->alloc<double>((int64_t)mp * mp);
+  if (grow_pred) {
+    GPR_HIP(hipStreamSynchronize(s));
+    release_buf(p, p->predA);
+    release_buf(p, p->predB);
+    p->pred_rows = 0;
+    p->predA = p->alloc<char>(chunk * mp * p->esz);
+    p->predB = p->alloc<char>(chunk * mp * p->esz);
+    p->pred_rows = chunk;
+  }
+  ensure_predict_scratch(p, chunk);
+  if (grow_pg) {
+    GPR_HIP(hipStreamSynchronize(s));
+    release_buf(p, p->pg_buf);
+    p->pg_rows = 0;
+    p->pg_buf = p->alloc<double>(pg_len);
+    p->pg_rows = chunk;
+    p->pg_host = pg_host;
+    p->pg_proj = pg_proj;
+  }
+  const int64_t pgr = p->pg_rows;
+  double* const stage_g[2] = {p->pg_buf, p->pg_buf ? p->pg_buf + pgr * D : nullptr};                     // [rows][D] (host part)
+  double* const stage_p0 = p->pg_buf ? p->pg_buf + (p->pg_host ? 2 * pgr * D : 0) : nullptr;
+  double* const stage_p[2] = {stage_p0, stage_p0 ? stage_p0 + pgr * d : nullptr};                        // [rows][d] (projection)
+  double* const bufA = static_cast<double*>(chunk > p->chunk ? p->predA : p->bufA);
+  double* const bufB = static_cast<double*>(chunk > p->chunk ? p->predB : p->bufB);
+  double* const rmean = p->prow;
+  double* const rvar = p->prow + p->xt_rows;
+  if (mats) ensure_predict_m(p);
+  const double add = predictive ? p->h.sigma2 : 0.0;
+  for (int64_t lo = 0; lo < nt; lo += chunk) {
+    const int rows = (int)std::min<int64_t>(chunk, nt - lo);
+    const int rows_p = (int)round_up(rows, TILE);
+    const double* xin = test_inputs + lo * D;
+    if (!on_device) {
+      GPR_HIP(hipMemcpy2DAsync(p->xt, (size_t)D * sizeof(double), test_inputs + lo * ld, (size_t)ld * sizeof(double),
+                               (size_t)D * sizeof(double), (size_t)rows, hipMemcpyHostToDevice, s));
+      xin = p->xt;
+    }
+    const double* pts = xin;
+    if (proj) {
+      launch_project(xin, rows, D, d, p->tproj, p->pt, s);
+      pts = p->pt;
+    }
+    // where the outputs of this chunk end up on the device, and where the kernel writes (d/dp in front of a projection)
+    double* const mean_dev = means ? (on_device ? means + lo : rmean) : nullptr;
+    double* const var_dev = variances ? (on_device ? variances + lo : rvar) : nullptr;
+    double* const dst[2] = {dmeans ? (on_device ? dmeans + lo * D : stage_g[0]) : nullptr,
+                            dvariances ? (on_device ? dvariances + lo * D : stage_g[1]) : nullptr};
+    double* const kout[2] = {dst[0] ? (proj ? stage_p[0] : dst[0]) : nullptr, dst[1] ? (proj ? stage_p[1] : dst[1]) : nullptr};
+    const int64_t kld = proj ? d : D;
+    if (small) {  // few inducing points: the whole chunk in one kernel
+      tstart(p, "pg_grad");
+      SmallPredictGradArgs a;
+      a.cp = p->cp; a.pts = pts; a.Z = p->Z; a.shift = p->zshift; a.uinv = p->uinv; a.rinv = p->rinv; a.tvec = p->tvec;
+      a.rows = rows; a.m = p->m; a.mp = mp; a.d = d; a.want_var = want_var ? 1 : 0; a.add = add;
+      a.means = mean_dev; a.vars = var_dev; a.dmeans = kout[0]; a.dvars = kout[1]; a.ldg = kld;
+      launch_small_predict_grad(a, s);
+    } else {
+      if (mats) {
+        tstart(p, "pg_cov");
+        launch_cov_cross<double>(p->cp, pts, rows, rows_p, p->Z, p->m, mp, d, bufA, s);
+        tstop(p);
+        tstart(p, "pg_gemm");
+        GemmArgs g;  // G = K M
+        g.A = bufA; g.lda = mp; g.B = p->pg_m; g.ldb = mp; g.C = bufB; g.ldc = mp;
+        g.M = rows_p; g.N = mp; g.K = mp;
+        launch_gemm(OP_NN, g, s);
+        tstop(p);
+      }
+      tstart(p, "pg_grad");
+      PredictGradArgs a;
+      a.pts = pts; a.Z = p->Z; a.shift = p->zshift; a.tvec = p->tvec; a.G = mats ? bufB : nullptr;
+      a.rows = rows; a.m = p->m; a.mp = mp; a.d = d;
+      a.log_sf2 = p->cp.log_sf2; a.inv_ell2_05 = p->cp.inv_ell2_05; a.sf2 = p->cp.sf2; a.add = add;
+      a.means = mean_dev; a.vars = var_dev; a.dmeans = kout[0]; a.dvars = kout[1]; a.ldg = kld;
+      launch_predict_grad(a, s);
+    }
+    if (proj)
+      for (int q = 0; q < 2; ++q)
+        if (dst[q]) launch_input_grad_project(kout[q], rows, d, D, p->tproj, dst[q], D, s);
+    tstop(p);
+    if (!on_device) {
+      if (means) GPR_HIP(hipMemcpyAsync(means + lo, rmean, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, s));
+      if (variances) GPR_HIP(hipMemcpyAsync(variances + lo, rvar, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, s));
+      double* const host[2] = {dmeans, dvariances};
+      for (int q = 0; q < 2; ++q)
+        if (host[q])
+          GPR_HIP(hipMemcpy2DAsync(host[q] + lo * ldg, (size_t)ldg * sizeof(double), dst[q], (size_t)D * sizeof(double),
+                                   (size_t)D * sizeof(double), (size_t)rows, hipMemcpyDeviceToHost, s));
+    }
+    GPR_HIP(hipStreamSynchronize(s));  // the chunk buffers are reused by the next chunk; device outputs are complete
+  }
+  if (p->timer.on) tcollect(p);
 }
 
 // Temporary device memory of one posterior call (sizes depend on the number of test points).
@@ -2308,6 +2500,7 @@ void do_load_predictor(gprhip_problem* p, const gprhip_hypers* h, const double* 
   p->have_model = p->have_factors = p->have_v = p->have_k = false;
   p->multi_state = false;
   p->cond_km = -1.0;
+  p->pg_m_valid = false;
   upload_hypers(p, h);
   std::vector<double> t(mp, 0.0);
   if (coeffs) std::memcpy(t.data(), coeffs, (size_t)m * sizeof(double));
@@ -3167,6 +3360,38 @@ int gprhip_predict(gprhip_problem* p, const double* test_inputs, int64_t ld, int
     if (p->f32) do_predict<float>(p, test_inputs, ld, nt, predictive, means, variances);
     else do_predict<double>(p, test_inputs, ld, nt, predictive, means, variances);
   });
+}
+
+int gprhip_predict_input_grad(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_t nt, int predictive,
+                              double* means, double* variances, double* dmeans, double* dvariances, int64_t ldg,
+                              int on_device) {
+  return guarded([&] {
+    if (!p || !test_inputs || nt < 1) {
+      set_error("gprhip_predict_input_grad: invalid arguments");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (!means && !variances && !dmeans && !dvariances) {
+      set_error("gprhip_predict_input_grad: all four outputs are NULL");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (p->f32) {
+      set_error("gprhip_predict_input_grad: the prediction gradient is evaluated in fp64 only (GPRHIP_F32_BULK problem)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (p->d > 64) {
+      set_error("gprhip_predict_input_grad: at most 64 point dimensions on the kernel side (d)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (on_device ? ld != p->D : ld < p->D) {
+      set_error("gprhip_predict_input_grad: bad ld (need ld == D for device buffers, ld >= D for host buffers)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if ((dmeans || dvariances) && (on_device ? ldg != p->D : ldg < p->D)) {
+      set_error("gprhip_predict_input_grad: bad ldg (need ldg == D for device buffers, ldg >= D for host buffers)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    do_predict_input_grad(p, test_inputs, ld, nt, predictive, means, variances, dmeans, dvariances, ldg, on_device);
+  }, p);
 }
 
 int gprhip_train_stats(gprhip_problem* p, double* means, double* sums) {

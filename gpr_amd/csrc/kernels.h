@@ -267,6 +267,40 @@ void launch_input_grad(const InputGradArgs& a, hipStream_t s);
 void launch_input_grad_project(const double* G, int64_t rows, int d, int D, const double* tproj, double* out, int64_t ldo,
                                hipStream_t s);
 
+// ---- gradients of the predictive mean and variance with respect to the test inputs (predict_grad.hip).  For one chunk of test
+// points, with E_mean = K .* (1 t^T), E_var = K .* G and G = K M, M = U^-1 (I - R~^-1 R~^-T) U^-T:
+//   means = rowsum(E_mean), vars = sf2 - rowsum(E_var) + add,
+//   dmeans[r][k] = -inv_ell2 ((p_rk - s_k) rowsum(E_mean)_r - (E_mean (Z - s))_rk),  dvars[r][k] = 2 inv_ell2 (... E_var ...)
+// Sixteen test points belong to one wavefront, which walks the columns in order: no atomics, the same bits every run.
+struct PredictGradArgs {
+  const double* pts;     // [rows][d]  test points (iso) or their projections (fat)
+  const double* Z;       // [mp][d]
+  const double* shift;   // [d] common offset s (the centroid of the inducing points)
+  const double* tvec;    // [mp] mean coefficients
+  const double* G;       // [rows_p][mp]  G = K M of the chunk: rows < rows and columns < round_up(m, 16) are read; null: the
+                         //     mean part alone (vars / dvars are then not written)
+  int rows, m, mp, d;    // d <= 64
+  double log_sf2, inv_ell2_05, sf2, add;  // add: sigma2 for predictive variances, else 0
+  double *means, *vars;  // out [rows]; either may be null
+  double *dmeans, *dvars;  // out [rows][ldg], columns < d written; either may be null
+  int64_t ldg;
+};
+void launch_predict_grad(const PredictGradArgs& a, hipStream_t s);
+// the same four outputs for at most 64 inducing points of at most 16 dimensions in one kernel per chunk (the shapes of
+// launch_small_predict): G is formed from the 64 x 64 corners of U^-1 and R~^-1 in LDS
+struct SmallPredictGradArgs {
+  CovParams cp;
+  const double *pts, *Z, *shift, *uinv, *rinv, *tvec;
+  int rows, m, mp, d;
+  int want_var;          // 0: the mean part alone (uinv / rinv are not read, vars / dvars not written)
+  double add;
+  double *means, *vars, *dmeans, *dvars;
+  int64_t ldg;
+};
+void launch_small_predict_grad(const SmallPredictGradArgs& a, hipStream_t s);
+// out (mp x mp, full) = I - B for a symmetric B valid on its upper tiles
+void launch_identity_minus_sym(const double* B, int mp, double* out, hipStream_t s);
+
 // ---- m x m finalisation (finalize.hip)
 // dst (upper tiles) = base + sum_z slices[z]; the diagonal tiles sum the first nslices_diag slices only (0 = nslices;
 // gemm_syrk_diag_slices for the result of a SYRK-shaped engine launch)

@@ -400,8 +400,14 @@ def _make_variant(spec, variational, functor, cov_kind="FITC"):
         get_inducing=lambda mp: mp.inducing_points if isinstance(mp, _Standalone)
         else mp.model.inputs.inducing.points,
         get_coeffs=lambda mp: mp.coeffs if isinstance(mp, _Standalone) else mp.evaluation().coeffs)
+    def _predict_input_grad(owner, inputs, which, sigma2=0.0):
+        """D x nt gradient of the predictive means / variances with respect to the test inputs (gprhip_predict_input_grad: an
+        extension beyond the reference's implemented surface, which only names calc_mpi_deriv in Sigs.Optimizer)"""
+        return _problem_of(owner, inputs, sigma2).predict_input_grad(inputs.points, predictive=False, want=(which,))[which]
+
     Eval.Means = SimpleNamespace(
         calc=lambda mean_predictor, inputs: _predict(mean_predictor, inputs, False, False)[0],  # :418-425
+        calc_input_gradient=lambda mean_predictor, inputs: _predict_input_grad(mean_predictor, inputs, "dmeans"),
         get=lambda means: means)
     Eval.Co_variance_predictor = SimpleNamespace(
         calc_model=lambda model: model,                                                    # :438-444
@@ -430,6 +436,7 @@ def _make_variant(spec, variational, functor, cov_kind="FITC"):
     Eval.Variances = SimpleNamespace(
         calc_model_inputs=variances_calc_model_inputs,
         calc=variances_calc,                                                                   # :498-518
+        calc_input_gradient=lambda cvp, sigma2, inputs: _predict_input_grad(cvp, inputs, "dvariances", sigma2),
         get=lambda v, predictive=True: v.variances + v.sigma2 if predictive else v.variances)  # :520-529
 
     # ---- single-point prediction (Input / Mean / Variance, lib/fitc_gp.ml:88-101, :402-414, :447-482)

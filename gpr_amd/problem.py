@@ -231,6 +231,47 @@ class Problem:
                                             _f64_ptr(var) if want_variances else None))
         return means, var
 
+    PREDICT_OUTPUTS = ("means", "variances", "dmeans", "dvariances")
+
+    def predict_input_grad(self, test_inputs, predictive=True, want=PREDICT_OUTPUTS, out_device_ptrs=None, nt=None, ldg=None):
+        """Means and variances as `predict`, and their gradients with respect to the test inputs (gprhip_predict_input_grad):
+        a dict with the names in `want` -- means / variances [nt], dmeans / dvariances D x nt in the layout of the test
+        inputs.  A request without variances and dvariances runs the mean part alone.
+        out_device_ptrs: {name: device address} for the names in `want` (means / variances: nt doubles, the gradients
+        point-major [nt][D]); `test_inputs` is then the device address of a contiguous point-major [nt][D] fp64 array of
+        `nt` points, the outputs are written in place and None is returned.
+        ldg (host output only): leading dimension >= D of the gradient buffers; rows D.. are not written (they hold NaN).
+        fp64 problems, no multiscales, at most 64 point dimensions on the kernel side (the library refuses otherwise)."""
+        want = tuple(want)
+        unknown = [w for w in want if w not in self.PREDICT_OUTPUTS]
+        if unknown:
+            raise ValueError("predict_input_grad: unknown outputs %s" % unknown)
+        null = C.c_void_p(None)
+        if out_device_ptrs is not None:
+            if nt is None:
+                raise ValueError("predict_input_grad: device buffers need nt")
+            ptrs = [C.c_void_p(int(out_device_ptrs[w])) if w in want else null for w in self.PREDICT_OUTPUTS]
+            _lib.check(self._lib.gprhip_predict_input_grad(self._handle(), C.c_void_p(int(test_inputs)), self.D, int(nt),
+                                                           int(predictive), *ptrs, self.D, 1))
+            return None
+        xt = np.asfortranarray(test_inputs, dtype=np.float64)
+        if xt.ndim != 2 or xt.shape[0] != self.D:
+            raise ValueError("predict_input_grad: expected test inputs of shape (%d, nt)" % self.D)
+        nt = xt.shape[1]
+        ldv = self.D if ldg is None else int(ldg)
+        out = {}
+        for w in want:
+            out[w] = (np.empty(nt, dtype=np.float64) if w in ("means", "variances")
+                      else np.full((max(ldv, 1), nt), np.nan, dtype=np.float64, order="F"))
+        ptrs = [C.c_void_p(out[w].ctypes.data) if w in out else null for w in self.PREDICT_OUTPUTS]
+        _lib.check(self._lib.gprhip_predict_input_grad(self._handle(), C.c_void_p(xt.ctypes.data), self.D, nt, int(predictive),
+                                                       *ptrs, ldv, 0))
+        if ldg is None:
+            for w in ("dmeans", "dvariances"):
+                if w in out:
+                    out[w] = out[w][:self.D]
+        return out
+
     def train_stats(self, want_means=False):
         """Residual sums of the training set under the last evaluation's mean coefficients
         (Trained.calc_means + the loops of Stats.calc, lib/fitc_gp.ml:296-297, :353-373).

@@ -327,6 +327,37 @@ int gprhip_predict(gprhip_problem* p, const double* test_inputs, int64_t ld, int
                    double* means, double* variances);
 int gprhip_predict_targets(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_t nt, double* means);
 
+/* Means and variances as gprhip_predict, together with their gradients with respect to the test inputs -- what maximising
+ * an acquisition function over candidate points, propagating an input uncertainty, a sensitivity analysis or a feature
+ * extractor in front of the GP at prediction time needs (an extension beyond the reference's implemented surface).  With
+ * p_r the point the kernel sees (x*_r, or tproj^T x*_r), K_rc = k(p_r, z_c), t the mean coefficients and
+ *   M = U^-1 (I - R~^-1 R~^-T) U^-T  (= (K_m + jitter)^-1 - B^-1),   G = K M:
+ *   means[r]     = sum_c K_rc t_c                            dmeans[:, r]     = tproj (-inv_ell2 sum_c K_rc t_c  (p_r - z_c))
+ *   variances[r] = sf2 - sum_c K_rc G_rc (+ sigma2)          dvariances[:, r] = tproj (2 inv_ell2 sum_c K_rc G_rc (p_r - z_c))
+ * (inv_ell2 = exp(-2 log_ell) for Cov_se_iso, 1 for Cov_se_fat; the tproj factor only with a projection).  `predictive`
+ * adds sigma2 to the variances only; the gradients do not depend on it.
+ *   on_device = 0: test_inputs is a host buffer, Fortran D x nt, ld >= D; means / variances are nt doubles on the host;
+ *                  dmeans / dvariances are host buffers, Fortran D x nt, ldg >= D (rows D..ldg-1 of every column are left
+ *                  untouched).
+ *   on_device = 1: all five are device pointers on the problem's device, the inputs and gradients point-major [nt][D] with
+ *                  ld == ldg == D; the outputs are written in place and are complete when the call returns.
+ * Each of the four outputs may be NULL; all four NULL is GPRHIP_EBADARG.  A request without variances and dvariances forms
+ * neither M nor G.
+ * State: as gprhip_predict -- GPRHIP_ESTATE without a completed evaluation or a loaded predictor, for variances /
+ * dvariances on a loaded predictor without factors, and for means / dmeans after gprhip_eval_targets; the fp32-bulk
+ * coefficient guard applies to means / dmeans.
+ * Limits: fp64 problems, one device, no multiscales in the model state, at most 64 point dimensions on the kernel side (d;
+ * D in front of a projection may be anything).  Anything outside them is GPRHIP_EBADARG.  A refused call enqueues nothing
+ * and leaves the state valid; the call never changes the predictor state.
+ * Memory: M (m x m, padded) is formed once per model state and kept until the next evaluation or gprhip_load_predictor;
+ * its allocation and the gradient staging buffers are compared with the device's free memory first: GPRHIP_EOOM leaves
+ * everything as it was.  Test points go through in the chunks of gprhip_predict.
+ * Stage timers: "pg_m" (M), and per chunk "pg_cov" (K), "pg_gemm" (G = K M), "pg_grad" (the gradient kernel; for at most 64
+ * inducing points of at most 16 dimensions the whole chunk is this one kernel). */
+int gprhip_predict_input_grad(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_t nt, int predictive,
+                              double* means, double* variances, double* dmeans, double* dvariances, int64_t ldg,
+                              int on_device);
+
 /* Training-set residual statistics with the model state left by the last evaluation (which must have had
  * targets): means[i] = K_nm[i,:] . coeffs over the resident training inputs (Trained.calc_means,
  * lib/fitc_gp.ml:296-297; host, n doubles, may be NULL) and

@@ -680,6 +680,16 @@ struct Make_deriv {
         check(gprhip_predict(p.get(), in.points->data(), in.points->rows, in.points->cols, 0, means.data(), nullptr));
         return means;
       }
+      // D x nt gradient of the means with respect to the test inputs (gprhip_predict_input_grad: an extension beyond the
+      // reference's implemented surface; fp64 problems, no multiscales, at most 64 point dimensions on the kernel side)
+      template <class Owner>
+      static Mat calc_input_gradient(const Owner& mean_predictor, const Inputs_t& in) {
+        Problem& p = problem_for(mean_predictor, in, "Means.calc_input_gradient");
+        Mat g(in.points->rows, in.points->cols);
+        check(gprhip_predict_input_grad(p.get(), in.points->data(), in.points->rows, in.points->cols, 0, nullptr, nullptr,
+                                        g.data(), nullptr, in.points->rows, 0));
+        return g;
+      }
     };
     struct Variances {
       template <class Owner>
@@ -689,6 +699,15 @@ struct Make_deriv {
         check(gprhip_predict(p.get(), in.points->data(), in.points->rows, in.points->cols, 0, nullptr,
                              v.variances.data()));
         return v;
+      }
+      // D x nt gradient of the variances with respect to the test inputs (the same for predictive and latent variances)
+      template <class Owner>
+      static Mat calc_input_gradient(const Owner& cvp, double sigma2, const Inputs_t& in) {
+        Problem& p = problem_of(cvp, in, "Variances.calc_input_gradient", sigma2);
+        Mat g(in.points->rows, in.points->cols);
+        check(gprhip_predict_input_grad(p.get(), in.points->data(), in.points->rows, in.points->cols, 0, nullptr, nullptr,
+                                        nullptr, g.data(), in.points->rows, 0));
+        return g;
       }
       static Vec get(const Variances_t& v, bool predictive = true) {  // :520-529
         Vec out = v.variances;
