@@ -51,6 +51,9 @@ external n_hypers : problem -> int -> int = "gprhip_ml_n_hypers"
 external predict : problem -> mat -> bool -> vec -> vec option -> unit = "gprhip_ml_predict"
 (* gradients of the predictive means / variances with respect to the test inputs (D x nt each; either may be None) *)
 external predict_input_grad : problem -> mat -> mat option -> mat option -> unit = "gprhip_ml_predict_input_grad"
+(* an acquisition criterion over the points and its gradient with respect to them (gprhip_acquire); the vector is
+   [| kind; maximise; predictive; best; xi; kappa; var_floor |], kind 0 EI, 1 log EI, 2 PI, 3 bound *)
+external acquire : problem -> vec -> mat -> vec option -> mat option -> unit = "gprhip_ml_acquire"
 external train_stats : problem -> vec option -> vec -> unit = "gprhip_ml_train_stats"
 external covariances : problem -> mat -> int -> bool -> mat -> unit = "gprhip_ml_covariances"
 external cov_samples : problem -> mat -> float -> float -> vec -> mat -> mat -> unit

@@ -162,6 +162,35 @@ CAMLprim value gprhip_ml_predict_input_grad(value prob, value points, value dmea
   CAMLreturn(Val_unit);
 }
 
+/* external acquire : problem -> vec -> mat -> values:vec option -> dvalues:mat option -> unit
+ *   an acquisition criterion over the points and its gradient (D x nt); the vector is
+ *   [| kind; maximise; predictive; best; xi; kappa; var_floor |] (gprhip_acquisition, the three integers as floats) */
+CAMLprim value gprhip_ml_acquire(value prob, value params, value points, value values, value dvalues) {
+  CAMLparam5(prob, params, points, values, dvalues);
+  struct caml_ba_array* ba = Caml_ba_array_val(points);
+  gprhip_problem* p = Problem_val(prob);
+  const double* x = (const double*)ba->data;
+  int64_t ld = ba->dim[0], nt = ba->dim[1];
+  double* a = (double*)opt_data(values);
+  double* da = (double*)opt_data(dvalues);
+  const double* par = (const double*)Caml_ba_data_val(params);
+  gprhip_acquisition acq;
+  int status;
+  if (Caml_ba_array_val(params)->dim[0] != 7) caml_invalid_argument("Gpr_hip.acquire: seven parameters");
+  acq.kind = (int)par[0];
+  acq.maximise = par[1] != 0.0;
+  acq.predictive = par[2] != 0.0;
+  acq.best = par[3];
+  acq.xi = par[4];
+  acq.kappa = par[5];
+  acq.var_floor = par[6];
+  caml_release_runtime_system();
+  status = gprhip_acquire(p, &acq, x, ld, nt, a, da, ld, NULL, NULL, 0, NULL, NULL, NULL, 0);
+  caml_acquire_runtime_system();
+  check(status);
+  CAMLreturn(Val_unit);
+}
+
 /* external train_stats : problem -> means:vec option -> sums:vec -> unit      sums = [sse; sum|e|; max|e|; sum y^2] */
 CAMLprim value gprhip_ml_train_stats(value prob, value means, value sums) {
   CAMLparam3(prob, means, sums);

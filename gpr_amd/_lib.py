@@ -81,6 +81,21 @@ class TargetsResult(C.Structure):
     ]
 
 
+class Acquisition(C.Structure):
+    """gprhip_acquisition: the criterion of gprhip_acquire (include/gprhip.h)."""
+    _fields_ = [
+        ("kind", C.c_int),
+        ("maximise", C.c_int),
+        ("predictive", C.c_int),
+        ("best", C.c_double),
+        ("xi", C.c_double),
+        ("kappa", C.c_double),
+        ("var_floor", C.c_double),
+    ]
+
+
+ACQ_EI, ACQ_LOG_EI, ACQ_PI, ACQ_BOUND = range(4)
+MAX_TOP_K = 64    # GPRHIP_MAX_TOP_K
 MAX_TARGETS = 16  # GPRHIP_MAX_TARGETS
 MAX_BATCH = 64    # GPRHIP_MAX_BATCH
 
@@ -116,6 +131,8 @@ SIGNATURES = {
     "gprhip_set_timing": (C.c_int, [_vp, C.c_int]),
     "gprhip_predict": (C.c_int, [_vp, _dp, C.c_int64, C.c_int64, C.c_int, _dp, _dp]),
     "gprhip_predict_input_grad": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, _vp, _vp, _vp, _vp, C.c_int64, C.c_int]),
+    "gprhip_acquire": (C.c_int, [_vp, C.POINTER(Acquisition), _vp, C.c_int64, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, C.c_int,
+                                 C.POINTER(C.c_int64), _dp, _dp, C.c_int]),
     "gprhip_predict_targets": (C.c_int, [_vp, _dp, C.c_int64, C.c_int64, _dp]),
     "gprhip_train_stats": (C.c_int, [_vp, _dp, _dp]),
     "gprhip_covariances": (C.c_int, [_vp, _dp, C.c_int64, C.c_int64, C.c_int, C.c_int, _dp]),

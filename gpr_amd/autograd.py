@@ -11,7 +11,10 @@ its gradient is written by the library straight into a fresh tensor (gprhip_eval
 inputs (gprhip_predict_input_grad, on_device = 1) -- an acquisition function over candidate points, an input uncertainty pushed
 through the model, a feature extractor in front of the GP at prediction time.
 
-torch is imported when `log_evidence` or `predict` is first called, not with this module: `import gpr_amd` never starts importing it.
+`acquire(problem, test_inputs, kind, ...)` is an acquisition criterion over candidate points (expected improvement, its
+logarithm, probability of improvement, a confidence bound) as a differentiable function of them (gprhip_acquire, on_device = 1).
+
+torch is imported when `log_evidence`, `predict` or `acquire` is first called, not with this module: `import gpr_amd` never starts importing it.
 """
 from __future__ import annotations
 
@@ -173,3 +176,57 @@ def predict(problem, test_inputs, predictive=True):
     float64 tensors.  One library call runs in forward; backward returns g_mean[:, None] * dmeans + g_var[:, None] * dvariances.
     predictive=True adds sigma2 to the variances (not to the gradients)."""
     return _predict_function().apply(problem, bool(predictive), test_inputs)
+
+
+_acquire_fn = None
+
+
+def _acquire_function():
+    """The torch.autograd.Function of `acquire`, made at first use."""
+    global _acquire_fn
+    if _acquire_fn is not None:
+        return _acquire_fn
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class _Acquire(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, problem, kind, kw, x):
+            D = problem.D
+            if x.dtype != torch.float64 or x.dim() != 2 or x.shape[1] != D or not x.is_contiguous() or not x.is_cuda:
+                raise ValueError("acquire: test_inputs must be a contiguous (nt, %d) float64 tensor on the problem's device" % D)
+            if x.device.index != problem.device:
+                raise ValueError("acquire: test_inputs live on device %s, the problem on device %d"
+                                 % (x.device.index, problem.device))
+            nt = int(x.shape[0])
+            values = torch.empty(nt, dtype=torch.float64, device=x.device)
+            ptrs = {"values": values.data_ptr()}
+            if ctx.needs_input_grad[3]:
+                ctx.dvalues = torch.empty((nt, D), dtype=torch.float64, device=x.device)
+                ptrs["dvalues"] = ctx.dvalues.data_ptr()
+            # the library works on its own stream: what produced the tensor must be complete before it reads it (its own
+            # outputs are complete when the call returns)
+            torch.cuda.current_stream(x.device).synchronize()
+            problem.acquire(x.data_ptr(), kind, want=tuple(ptrs), out_device_ptrs=ptrs, nt=nt, **kw)
+            return values
+
+        @staticmethod
+        @once_differentiable  # (the stored gradient is numbers, not a graph: a second derivative raises instead of being zero)
+        def backward(ctx, g):
+            if not ctx.needs_input_grad[3]:
+                return None, None, None, None
+            return None, None, None, g[:, None] * ctx.dvalues
+
+    _acquire_fn = _Acquire
+    return _acquire_fn
+
+
+def acquire(problem, test_inputs, kind, **kw):
+    """The acquisition criterion `kind` ("ei" | "log_ei" | "pi" | "bound") of `problem`'s current model state at `test_inputs`,
+    an (nt, D) contiguous float64 tensor on the problem's device, as an (nt,) float64 tensor; every criterion is "larger is
+    better".  kw: maximise (required), best, xi, kappa, var_floor, predictive -- those of Problem.acquire.  One library call
+    runs in forward; backward returns g[:, None] * dvalues."""
+    extra = set(kw) - {"maximise", "best", "xi", "kappa", "var_floor", "predictive"}
+    if extra:
+        raise TypeError("acquire: unknown arguments %s" % sorted(extra))
+    return _acquire_function().apply(problem, kind, dict(kw), test_inputs)

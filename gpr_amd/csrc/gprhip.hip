@@ -276,6 +276,10 @@ struct gprhip_problem {
   double* pg_buf = nullptr;  // gradient staging of one chunk: [2][rows][D] for a host destination + [2][rows][d] dp (projection)
   int64_t pg_rows = 0;       // rows it holds
   bool pg_host = false, pg_proj = false;  // ... with those two parts
+  // gprhip_acquire's selection: candidate lists of the slabs (device), the block of a piece's k winners [k (D + 2)] on the
+  // device and its pinned mirror; made at the first call with top_k > 0
+  void* acq_scratch = nullptr;
+  double *acq_out = nullptr, *acq_host = nullptr;
   bool use_small() const {
     return !multi && !xg_engine && small_path && !f32 && !engine_steps && small_path_fits(m, mp, d, has_proj() ? D : 0, n, has_ms());
   }
@@ -2004,6 +2008,93 @@ void ensure_predict_m(gprhip_problem* p) {
   p->pg_m_valid = true;
 }
 
+// The buffers of one call of gprhip_predict_input_grad / gprhip_acquire: the chunk rule of do_predict, M, the chunk buffers and
+// the gradient staging, allocated after a look at the device's free memory (a refusal leaves the problem as it was).
+// want_var: K and G of a chunk are needed (matrices in memory unless the one-kernel path serves the shape);
+// host_g: a gradient matrix is staged on the device ([rows][D]) in front of a transfer
+struct PgPlan {
+  int64_t chunk;
+  bool small, mats, proj;
+  double *stage_g[2], *stage_p[2];  // gradient staging [rows][D] (host part) and [rows][d] (in front of the projection)
+  double *bufA, *bufB;              // K and G of a chunk
+  double *rmean, *rvar, *rval;      // three row vectors of xt_rows entries
+};
+PgPlan pg_prepare(gprhip_problem* p, const char* fn, int64_t nt, bool want_var, bool host_g) {
+  hipStream_t s = p->stream;
+  const int mp = p->mp, D = p->D, d = p->d;
+  const bool proj = p->has_proj();
+  const bool small = p->small_path && p->m <= 64 && mp == TILE && d <= 16;
+  const bool mats = !small && want_var;  // K and G of a chunk are matrices in memory
+  // the chunk rule of do_predict
+  int64_t chunk = p->chunk;
+  const int64_t want = std::min<int64_t>(131072, round_up(nt, TILE));
+  bool grow_pred = false;
+  if (want > chunk) {
+    const int64_t rows = std::min<int64_t>(131072, std::max(want, 8 * chunk));
+    if (mats) {
+      grow_pred = p->pred_rows < want;
+      chunk = grow_pred ? rows : p->pred_rows;
+    } else {
+      chunk = std::max(p->xt_rows >= want ? p->xt_rows : rows, p->chunk);
+    }
+  }
+  // everything this call allocates, after a look at the device's free memory: a refusal leaves the problem as it was
+  const bool need_m = mats && !p->pg_m;
+  const bool grow_xt = !(p->xt && p->xt_rows >= chunk);
+  const bool grow_pg = (host_g || proj) && (p->pg_rows < chunk || (host_g && !p->pg_host) || (proj && !p->pg_proj));
+  const bool pg_host = host_g || p->pg_host, pg_proj = proj || p->pg_proj;
+  const int64_t pg_len = 2 * chunk * ((pg_host ? D : 0) + (pg_proj ? d : 0));
+  {
+    int64_t need = 0;
+    if (need_m) need += (int64_t)mp * mp * 8;
+    if (grow_pred) need += 2 * chunk * mp * 8;
+    if (grow_xt) need += chunk * (D + d + 3) * 8;
+    if (grow_pg) need += pg_len * 8;
+    if (need > 0) {
+      size_t free_b = 0, total_b = 0;
+      GPR_HIP(hipMemGetInfo(&free_b, &total_b));
+      if ((size_t)need + (size_t(64) << 20) > free_b) {
+        set_error(std::string(fn) + ": not enough device memory for M and the chunk buffers of the prediction gradient");
+        throw HipFail{ST_OOM};
+      }
+    }
+  }
+  if (need_m) p->pg_m = p->alloc<double>((int64_t)mp * mp);
+  if (grow_pred) {
+    GPR_HIP(hipStreamSynchronize(s));
+    release_buf(p, p->predA);
+    release_buf(p, p->predB);
+    p->pred_rows = 0;
+    p->predA = p->alloc<char>(chunk * mp * p->esz);
+    p->predB = p->alloc<char>(chunk * mp * p->esz);
+    p->pred_rows = chunk;
+  }
+  ensure_predict_scratch(p, chunk);
+  if (grow_pg) {
+    GPR_HIP(hipStreamSynchronize(s));
+    release_buf(p, p->pg_buf);
+    p->pg_rows = 0;
+    p->pg_buf = p->alloc<double>(pg_len);
+    p->pg_rows = chunk;
+    p->pg_host = pg_host;
+    p->pg_proj = pg_proj;
+  }
+  const int64_t pgr = p->pg_rows;
+  PgPlan plan;
+  plan.chunk = chunk; plan.small = small; plan.mats = mats; plan.proj = proj;
+  plan.stage_g[0] = p->pg_buf;                                               // [rows][D] (host part)
+  plan.stage_g[1] = p->pg_buf ? p->pg_buf + pgr * D : nullptr;
+  double* const stage_p0 = p->pg_buf ? p->pg_buf + (p->pg_host ? 2 * pgr * D : 0) : nullptr;
+  plan.stage_p[0] = stage_p0;                                                // [rows][d] (projection)
+  plan.stage_p[1] = stage_p0 ? stage_p0 + pgr * d : nullptr;
+  plan.bufA = static_cast<double*>(chunk > p->chunk ? p->predA : p->bufA);
+  plan.bufB = static_cast<double*>(chunk > p->chunk ? p->predB : p->bufB);
+  plan.rmean = p->prow;
+  plan.rvar = p->prow + p->xt_rows;
+  plan.rval = p->prow + 2 * p->xt_rows;
+  return plan;
+}
+
 // Means / variances of do_predict and their gradients with respect to the test inputs (predict_grad.hip), chunk by chunk with
 // do_predict's buffers and chunk rule.  The caller has checked the arguments and the limits.
 void do_predict_input_grad(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_t nt, int predictive, double* means,
@@ -2030,72 +2121,12 @@ void do_predict_input_grad(gprhip_problem* p, const double* test_inputs, int64_t
   GPR_HIP(hipSetDevice(p->device));
   hipStream_t s = p->stream;
   const int mp = p->mp, D = p->D, d = p->d;
-  const bool proj = p->has_proj();
-  const bool small = p->small_path && p->m <= 64 && mp == TILE && d <= 16;
-  const bool mats = !small && want_var;  // K and G of a chunk are matrices in memory
-  // the chunk rule of do_predict
-  int64_t chunk = p->chunk;
-  const int64_t want = std::min<int64_t>(131072, round_up(nt, TILE));
-  bool grow_pred = false;
-  if (want > chunk) {
-    const int64_t rows = std::min<int64_t>(131072, std::max(want, 8 * chunk));
-    if (mats) {
-      grow_pred = p->pred_rows < want;
-      chunk = grow_pred ? rows : p->pred_rows;
-    } else {
-      chunk = std::max(p->xt_rows >= want ? p->xt_rows : rows, p->chunk);
-    }
-  }
-  // everything this call allocates, after a look at the device's free memory: a refusal leaves the problem as it was
-  const bool host_g = !on_device && (dmeans || dvariances);
-  const bool need_m = mats && !p->pg_m;
-  const bool grow_xt = !(p->xt && p->xt_rows >= chunk);
-  const bool grow_pg = (host_g || proj) && (p->pg_rows < chunk || (host_g && !p->pg_host) || (proj && !p->pg_proj));
-  const bool pg_host = host_g || p->pg_host, pg_proj = proj || p->pg_proj;
-  const int64_t pg_len = 2 * chunk * ((pg_host ? D : 0) + (pg_proj ? d : 0));
-  {
-    int64_t need = 0;
-    if (need_m) need += (int64_t)mp * mp * 8;
-    if (grow_pred) need += 2 * chunk * mp * 8;
-    if (grow_xt) need += chunk * (D + d + 3) * 8;
-    if (grow_pg) need += pg_len * 8;
-    if (need > 0) {
-      size_t free_b = 0, total_b = 0;
-      GPR_HIP(hipMemGetInfo(&free_b, &total_b));
-      if ((size_t)need + (size_t(64) << 20) > free_b) {
-        set_error("gprhip_predict_input_grad: not enough device memory for M and the chunk buffers of the prediction gradient");
-        throw HipFail{ST_OOM};
-      }
-    }
-  }
-  if (need_m) p->pg_m = p->alloc<double>((int64_t)mp * mp);
-  if (grow_pred) {
-    GPR_HIP(hipStreamSynchronize(s));
-    release_buf(p, p->predA);
-    release_buf(p, p->predB);
-    p->pred_rows = 0;
-    p->predA = p->alloc<char>(chunk * mp * p->esz);
-    p->predB = p->alloc<char>(chunk * mp * p->esz);
-    p->pred_rows = chunk;
-  }
-  ensure_predict_scratch(p, chunk);
-  if (grow_pg) {
-    GPR_HIP(hipStreamSynchronize(s));
-    release_buf(p, p->pg_buf);
-    p->pg_rows = 0;
-    p->pg_buf = p->alloc<double>(pg_len);
-    p->pg_rows = chunk;
-    p->pg_host = pg_host;
-    p->pg_proj = pg_proj;
-  }
-  const int64_t pgr = p->pg_rows;
-  double* const stage_g[2] = {p->pg_buf, p->pg_buf ? p->pg_buf + pgr * D : nullptr};                     // [rows][D] (host part)
-  double* const stage_p0 = p->pg_buf ? p->pg_buf + (p->pg_host ? 2 * pgr * D : 0) : nullptr;
-  double* const stage_p[2] = {stage_p0, stage_p0 ? stage_p0 + pgr * d : nullptr};                        // [rows][d] (projection)
-  double* const bufA = static_cast<double*>(chunk > p->chunk ? p->predA : p->bufA);
-  double* const bufB = static_cast<double*>(chunk > p->chunk ? p->predB : p->bufB);
-  double* const rmean = p->prow;
-  double* const rvar = p->prow + p->xt_rows;
+  const PgPlan plan = pg_prepare(p, "gprhip_predict_input_grad", nt, want_var, !on_device && (dmeans || dvariances));
+  const bool proj = plan.proj, small = plan.small, mats = plan.mats;
+  const int64_t chunk = plan.chunk;
+  double* const stage_g[2] = {plan.stage_g[0], plan.stage_g[1]};
+  double* const stage_p[2] = {plan.stage_p[0], plan.stage_p[1]};
+  double *const bufA = plan.bufA, *const bufB = plan.bufB, *const rmean = plan.rmean, *const rvar = plan.rvar;
   if (mats) ensure_predict_m(p);
   const double add = predictive ? p->h.sigma2 : 0.0;
   for (int64_t lo = 0; lo < nt; lo += chunk) {
@@ -2160,6 +2191,167 @@ void do_predict_input_grad(gprhip_problem* p, const double* test_inputs, int64_t
                                    (size_t)D * sizeof(double), (size_t)rows, hipMemcpyDeviceToHost, s));
     }
     GPR_HIP(hipStreamSynchronize(s));  // the chunk buffers are reused by the next chunk; device outputs are complete
+  }
+  if (p->timer.on) tcollect(p);
+}
+
+// gprhip_acquire: the chunk loop of do_predict_input_grad with the criterion epilogue of the two kernels -- one value vector and
+// one gradient matrix instead of two --, and the best top_k candidates selected on the device chunk by chunk (acquire.hip),
+// the chunks' lists merged here with the same rule: value descending, the lower index first among equal values.
+// The caller has checked the arguments and the limits.
+void do_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const double* test_inputs, int64_t ld, int64_t nt,
+                double* values, double* dvalues, int64_t ldg, double* means, double* variances, int top_k, int64_t* top_index,
+                double* top_values, double* top_dvalues, int on_device) {
+  const bool want_var = !(acq->kind == GPRHIP_ACQ_BOUND && acq->kappa == 0.0) || variances;
+  if (!p->have_model || p->stage != 0) {
+    set_error("gprhip_acquire: no completed evaluation to predict from");
+    throw HipFail{ST_STATE};
+  }
+  if (p->has_ms()) {
+    set_error("gprhip_acquire: multiscales are not supported (the model state has log_multiscales_m05)");
+    throw HipFail{ST_BAD_ARG};
+  }
+  if (want_var && !p->have_factors) {
+    set_error("gprhip_acquire: the loaded predictor has no co-variance coefficients (chol_km, r_mat)");
+    throw HipFail{ST_STATE};
+  }
+  if (p->multi_state) {
+    set_error("gprhip_acquire: the last evaluation was gprhip_eval_targets (several target vectors): means and "
+              "their gradients are available after the next gprhip_eval");
+    throw HipFail{ST_STATE};
+  }
+  need_trustworthy_coeffs(p, "gprhip_acquire");
+  GPR_HIP(hipSetDevice(p->device));
+  hipStream_t s = p->stream;
+  const int mp = p->mp, D = p->D, d = p->d;
+  const bool want_grad = dvalues || (top_k > 0 && top_dvalues);
+  const bool stage_grad = want_grad && !(on_device && dvalues);  // the gradient of a chunk stays in the library's staging
+  const PgPlan plan = pg_prepare(p, "gprhip_acquire", nt, want_var, stage_grad);
+  const int64_t chunk = plan.chunk;
+  if (top_k > 0 && !p->acq_scratch) {
+    p->acq_scratch = p->alloc<char>(acq_select_scratch_bytes());
+    p->acq_out = p->alloc<double>((int64_t)ACQ_MAX_TOP_K * (D + 2));
+    GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->acq_host), (size_t)ACQ_MAX_TOP_K * (D + 2) * sizeof(double),
+                          hipHostMallocDefault));
+  }
+  if (plan.mats) ensure_predict_m(p);
+  AcqArgs q;
+  q.kind = acq->kind; q.s = acq->maximise ? 1.0 : -1.0; q.best = acq->best; q.xi = acq->xi; q.kappa = acq->kappa;
+  q.var_floor = acq->var_floor;
+  const double add = acq->predictive ? p->h.sigma2 : 0.0;
+  // the best so far, over the chunks done
+  std::vector<int64_t> best_idx;
+  std::vector<double> best_val, best_grad;
+  for (int64_t lo = 0; lo < nt; lo += chunk) {
+    const int rows = (int)std::min<int64_t>(chunk, nt - lo);
+    const int rows_p = (int)round_up(rows, TILE);
+    const double* xin = test_inputs + lo * D;
+    if (!on_device) {
+      GPR_HIP(hipMemcpy2DAsync(p->xt, (size_t)D * sizeof(double), test_inputs + lo * ld, (size_t)ld * sizeof(double),
+                               (size_t)D * sizeof(double), (size_t)rows, hipMemcpyHostToDevice, s));
+      xin = p->xt;
+    }
+    const double* pts = xin;
+    if (plan.proj) {
+      launch_project(xin, rows, D, d, p->tproj, p->pt, s);
+      pts = p->pt;
+    }
+    double* const mean_dev = means ? (on_device ? means + lo : plan.rmean) : nullptr;
+    double* const var_dev = variances ? (on_device ? variances + lo : plan.rvar) : nullptr;
+    double* const val_dev = (values && on_device) ? values + lo : ((values || top_k > 0) ? plan.rval : nullptr);
+    double* const dst = want_grad ? (stage_grad ? plan.stage_g[0] : dvalues + lo * D) : nullptr;
+    double* const kout = dst ? (plan.proj ? plan.stage_p[0] : dst) : nullptr;  // d/dp in front of a projection
+    const int64_t kld = plan.proj ? d : D;
+    q.values = val_dev;
+    if (plan.small) {  // few inducing points: the whole chunk in one kernel
+      tstart(p, "pg_grad");
+      SmallPredictGradArgs a;
+      a.cp = p->cp; a.pts = pts; a.Z = p->Z; a.shift = p->zshift; a.uinv = p->uinv; a.rinv = p->rinv; a.tvec = p->tvec;
+      a.rows = rows; a.m = p->m; a.mp = mp; a.d = d; a.want_var = want_var ? 1 : 0; a.add = add;
+      a.means = mean_dev; a.vars = var_dev; a.dmeans = kout; a.dvars = nullptr; a.ldg = kld;
+      launch_small_acquire_grad(a, q, s);
+    } else {
+      if (plan.mats) {
+        tstart(p, "pg_cov");
+        launch_cov_cross<double>(p->cp, pts, rows, rows_p, p->Z, p->m, mp, d, plan.bufA, s);
+        tstop(p);
+        tstart(p, "pg_gemm");
+        GemmArgs g;  // G = K M
+        g.A = plan.bufA; g.lda = mp; g.B = p->pg_m; g.ldb = mp; g.C = plan.bufB; g.ldc = mp;
+        g.M = rows_p; g.N = mp; g.K = mp;
+        launch_gemm(OP_NN, g, s);
+        tstop(p);
+      }
+      tstart(p, "pg_grad");
+      PredictGradArgs a;
+      a.pts = pts; a.Z = p->Z; a.shift = p->zshift; a.tvec = p->tvec; a.G = plan.mats ? plan.bufB : nullptr;
+      a.rows = rows; a.m = p->m; a.mp = mp; a.d = d;
+      a.log_sf2 = p->cp.log_sf2; a.inv_ell2_05 = p->cp.inv_ell2_05; a.sf2 = p->cp.sf2; a.add = add;
+      a.means = mean_dev; a.vars = var_dev; a.dmeans = kout; a.dvars = nullptr; a.ldg = kld;
+      launch_acquire_grad(a, q, s);
+    }
+    if (plan.proj && dst) launch_input_grad_project(kout, rows, d, D, p->tproj, dst, D, s);
+    tstop(p);
+    if (!on_device) {
+      if (values) GPR_HIP(hipMemcpyAsync(values + lo, val_dev, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, s));
+      if (means) GPR_HIP(hipMemcpyAsync(means + lo, plan.rmean, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, s));
+      if (variances)
+        GPR_HIP(hipMemcpyAsync(variances + lo, plan.rvar, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, s));
+      if (dvalues)
+        GPR_HIP(hipMemcpy2DAsync(dvalues + lo * ldg, (size_t)ldg * sizeof(double), dst, (size_t)D * sizeof(double),
+                                 (size_t)D * sizeof(double), (size_t)rows, hipMemcpyDeviceToHost, s));
+    }
+    // the best top_k of the chunk, in pieces of at most 256 slabs, before its buffers are reused
+    const int64_t piece_rows = (int64_t)ACQ_SELECT_MAX_SLABS * 2048;
+    for (int64_t po = 0; top_k > 0 && po < rows; po += piece_rows) {
+      const int pr = (int)std::min<int64_t>(piece_rows, rows - po);
+      const bool gather_g = top_dvalues != nullptr;
+      tstart(p, "acq_select");
+      AcqSelectArgs sel;
+      sel.values = val_dev + po; sel.rows = pr; sel.k = top_k; sel.grads = gather_g ? dst + po * D : nullptr; sel.D = D;
+      sel.scratch = p->acq_scratch; sel.out = p->acq_out;
+      launch_acq_select(sel, s);
+      tstop(p);
+      const int64_t blk = (int64_t)top_k * (gather_g ? D + 2 : 2);
+      GPR_HIP(hipMemcpyAsync(p->acq_host, p->acq_out, (size_t)blk * sizeof(double), hipMemcpyDeviceToHost, s));
+      GPR_HIP(hipStreamSynchronize(s));
+      // merge: both lists are sorted; an earlier entry (a lower index) stays in front of an equal later one
+      const double* const hi = p->acq_host;
+      const double* const hv = hi + top_k;
+      const double* const hg = hv + top_k;
+      std::vector<int64_t> m_idx;
+      std::vector<double> m_val, m_grad;
+      size_t ia = 0;
+      int ib = 0;
+      while ((int)m_idx.size() < top_k) {
+        const bool has_a = ia < best_idx.size(), has_b = ib < top_k && hi[ib] >= 0.0;
+        if (!has_a && !has_b) break;
+        if (has_a && (!has_b || !(hv[ib] > best_val[ia]))) {
+          m_idx.push_back(best_idx[ia]);
+          m_val.push_back(best_val[ia]);
+          if (gather_g) m_grad.insert(m_grad.end(), best_grad.begin() + ia * D, best_grad.begin() + (ia + 1) * D);
+          ++ia;
+        } else {
+          m_idx.push_back(lo + po + (int64_t)hi[ib]);
+          m_val.push_back(hv[ib]);
+          if (gather_g) m_grad.insert(m_grad.end(), hg + (int64_t)ib * D, hg + (int64_t)(ib + 1) * D);
+          ++ib;
+        }
+      }
+      best_idx.swap(m_idx);
+      best_val.swap(m_val);
+      best_grad.swap(m_grad);
+    }
+    GPR_HIP(hipStreamSynchronize(s));  // the chunk buffers are reused by the next chunk; device outputs are complete
+  }
+  for (int j = 0; j < top_k; ++j) {
+    if (j >= (int)best_idx.size()) {
+      top_index[j] = -1;  // fewer than top_k candidates qualify: their values and gradients are left as they are
+      continue;
+    }
+    top_index[j] = best_idx[j];
+    if (top_values) top_values[j] = best_val[j];
+    if (top_dvalues) std::copy(best_grad.begin() + (size_t)j * D, best_grad.begin() + (size_t)(j + 1) * D, top_dvalues + (int64_t)j * D);
   }
   if (p->timer.on) tcollect(p);
 }
@@ -2952,6 +3144,7 @@ void gprhip_problem_destroy(gprhip_problem* p) {
   if (p->ev_hy) hipEventDestroy(p->ev_hy);
   if (p->hy_host && !p->is_lane) hipHostFree(p->hy_host);
   if (p->res_host) hipHostFree(p->res_host);
+  if (p->acq_host) hipHostFree(p->acq_host);
   if (p->ev_fork) hipEventDestroy(p->ev_fork);
   if (p->ev_join) hipEventDestroy(p->ev_join);
   if (p->ev_rf) hipEventDestroy(p->ev_rf);
@@ -3391,6 +3584,67 @@ int gprhip_predict_input_grad(gprhip_problem* p, const double* test_inputs, int6
       throw HipFail{ST_BAD_ARG};
     }
     do_predict_input_grad(p, test_inputs, ld, nt, predictive, means, variances, dmeans, dvariances, ldg, on_device);
+  }, p);
+}
+
+int gprhip_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const double* test_inputs, int64_t ld, int64_t nt,
+                   double* values, double* dvalues, int64_t ldg, double* means, double* variances, int top_k,
+                   int64_t* top_index, double* top_values, double* top_dvalues, int on_device) {
+  return guarded([&] {
+    if (!acq) {
+      set_error("gprhip_acquire: invalid arguments (acq is NULL)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (acq->kind < GPRHIP_ACQ_EI || acq->kind > GPRHIP_ACQ_BOUND) {
+      set_error("gprhip_acquire: unknown kind (one of GPRHIP_ACQ_EI, _LOG_EI, _PI, _BOUND)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (!(acq->xi >= 0.0) || !(acq->kappa >= 0.0)) {
+      set_error("gprhip_acquire: xi and kappa must not be negative");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (!(acq->var_floor > 0.0) || !std::isfinite(acq->var_floor)) {
+      set_error("gprhip_acquire: var_floor must be positive and finite");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (!std::isfinite(acq->best)) {
+      set_error("gprhip_acquire: best must be finite");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (top_k < 0 || top_k > GPRHIP_MAX_TOP_K) {
+      set_error("gprhip_acquire: top_k must lie in 0 .. GPRHIP_MAX_TOP_K (64)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (top_k > 0 && !top_index) {
+      set_error("gprhip_acquire: top_k > 0 needs top_index");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (!values && !dvalues && !means && !variances && top_k == 0) {
+      set_error("gprhip_acquire: nothing is requested (the four outputs are NULL and top_k is 0)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (!p || !test_inputs || nt < 1) {
+      set_error("gprhip_acquire: invalid arguments");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (p->f32) {
+      set_error("gprhip_acquire: the prediction gradient is evaluated in fp64 only (GPRHIP_F32_BULK problem)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (p->d > 64) {
+      set_error("gprhip_acquire: at most 64 point dimensions on the kernel side (d)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (on_device ? ld != p->D : ld < p->D) {
+      set_error("gprhip_acquire: bad ld (need ld == D for device buffers, ld >= D for host buffers)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    if (dvalues && (on_device ? ldg != p->D : ldg < p->D)) {
+      set_error("gprhip_acquire: bad ldg (need ldg == D for device buffers, ldg >= D for host buffers)");
+      throw HipFail{ST_BAD_ARG};
+    }
+    do_acquire(p, acq, test_inputs, ld, nt, values, dvalues, ldg, means, variances, top_k, top_index, top_values, top_dvalues,
+               on_device);
   }, p);
 }
 

@@ -301,6 +301,34 @@ void launch_small_predict_grad(const SmallPredictGradArgs& a, hipStream_t s);
 // out (mp x mp, full) = I - B for a symmetric B valid on its upper tiles
 void launch_identity_minus_sym(const double* B, int mp, double* out, hipStream_t s);
 
+// ---- acquisition criteria over the test points (gprhip_acquire): the two kernels above with a criterion epilogue (acq_math.h).
+// Per test point, from its mean and variance (the doubles `means` / `vars` receive): the value a and c_mu = da/dmean,
+// c_v = da/dvariance; a goes to `values`, and a.dmeans receives the one matrix c_mu dmeans + c_v dvars, entry by entry from the
+// two doubles the plain kernel would have stored.  a.dvars is not used.  Without the variance part (a.G null / want_var 0) the
+// criterion is the bound with kappa = 0: a = s mean, gradient s dmeans.
+struct AcqArgs {
+  int kind;              // GPRHIP_ACQ_*
+  double s;              // +1: larger targets are better, -1: smaller
+  double best, xi, kappa, var_floor;
+  double* values;        // out [rows], or null
+};
+void launch_acquire_grad(const PredictGradArgs& a, const AcqArgs& q, hipStream_t s);
+void launch_small_acquire_grad(const SmallPredictGradArgs& a, const AcqArgs& q, hipStream_t s);
+// the k largest of values[0 .. rows) (acquire.hip): value descending, the lower index first among equal values, NaN never;
+// out = [k] indices as doubles (-1 where fewer than k qualify) | [k] values | [k][D] rows of grads (grads null: not written)
+constexpr int ACQ_MAX_TOP_K = 64;           // GPRHIP_MAX_TOP_K
+constexpr int ACQ_SELECT_MAX_SLABS = 256;   // slabs of 2048 values per launch: rows <= 524288
+struct AcqSelectArgs {
+  const double* values;  // [rows]
+  int rows, k;           // 1 <= k <= ACQ_MAX_TOP_K
+  const double* grads;   // [rows][D], or null
+  int D;
+  void* scratch;         // acq_select_scratch_bytes()
+  double* out;           // [k (D + 2)] (device)
+};
+int64_t acq_select_scratch_bytes();
+void launch_acq_select(const AcqSelectArgs& a, hipStream_t s);
+
 // ---- m x m finalisation (finalize.hip)
 // dst (upper tiles) = base + sum_z slices[z]; the diagonal tiles sum the first nslices_diag slices only (0 = nslices;
 // gemm_syrk_diag_slices for the result of a SYRK-shaped engine launch)

@@ -439,6 +439,17 @@ def _make_variant(spec, variational, functor, cov_kind="FITC"):
         calc_input_gradient=lambda cvp, sigma2, inputs: _predict_input_grad(cvp, inputs, "dvariances", sigma2),
         get=lambda v, predictive=True: v.variances + v.sigma2 if predictive else v.variances)  # :520-529
 
+    def acquisition_calc(trained, inputs, kind, **kw):
+        """An acquisition criterion over the test inputs with its D x nt gradient and, with top_k, the best candidates
+        (gprhip_acquire through Problem.acquire, whose keyword arguments and result these are: an extension beyond the
+        reference's implemented surface, which only names calc_mpi_deriv in Sigs.Optimizer).  `trained`: a trained model --
+        the criterion needs the mean and the variance predictor of one state."""
+        if not isinstance(trained, _Trained):
+            raise TypeError("Acquisition.calc: a trained model (the object of Trained.calc) is needed")
+        return _problem_of(trained, inputs).acquire(inputs.points, kind, **kw)
+
+    Eval.Acquisition = SimpleNamespace(calc=acquisition_calc)
+
     # ---- single-point prediction (Input / Mean / Variance, lib/fitc_gp.ml:88-101, :402-414, :447-482)
     class _Input:
         def __init__(self, inducing, point):

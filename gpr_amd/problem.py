@@ -145,6 +145,7 @@ class Problem:
              log_multiscales_m05=None, reuse_v=False):
         """reuse_v=True: only sigma2/targets changed since the previous eval on this problem
         (Model.update_sigma2, lib/fitc_gp.ml:234-236): K_nm, V and r are reused."""
+        self._log_sf2 = float(log_sf2)  # (Problem.acquire's default var_floor)
         h, keep = self._hypers(log_ell, log_sf2, sigma2, inducing, tproj, variational, model_only, jitter,
                                log_hetero_skedasticity, log_multiscales_m05, reuse_v)
         res = Result()
@@ -165,6 +166,7 @@ class Problem:
         array (the layout of `set_inputs_device`, e.g. tensor.data_ptr()) that receives it instead -- the second value is
         then None.  ld (host output only): leading dimension >= D of the returned array's buffer; rows D.. of it are not
         written (they hold NaN).  fp64 problems, no multiscales (the library refuses otherwise)."""
+        self._log_sf2 = float(log_sf2)  # (Problem.acquire's default var_floor)
         h, keep = self._hypers(log_ell, log_sf2, sigma2, inducing, tproj, variational, model_only, jitter,
                                log_hetero_skedasticity, log_multiscales_m05, reuse_v)
         res = Result()
@@ -190,6 +192,7 @@ class Problem:
                      log_multiscales_m05=None, reuse_v=False):
         """All target vectors of `set_targets_many` against one model in one evaluation: per-target evidence and mean
         coefficients, the gradient of the summed log evidence.  Keyword arguments as `eval` (model_only is refused)."""
+        self._log_sf2 = float(log_sf2)  # (Problem.acquire's default var_floor)
         h, keep = self._hypers(log_ell, log_sf2, sigma2, inducing, tproj, variational, model_only, jitter,
                                log_hetero_skedasticity, log_multiscales_m05, reuse_v)
         res = TargetsResult()
@@ -272,6 +275,67 @@ class Problem:
                     out[w] = out[w][:self.D]
         return out
 
+    ACQUIRE_KINDS = {"ei": _lib.ACQ_EI, "log_ei": _lib.ACQ_LOG_EI, "pi": _lib.ACQ_PI, "bound": _lib.ACQ_BOUND}
+    ACQUIRE_OUTPUTS = ("values", "dvalues", "means", "variances")
+
+    def acquire(self, test_inputs, kind, *, maximise, best=0.0, xi=0.0, kappa=0.0, var_floor=None, predictive=False,
+                want=("values", "dvalues"), top_k=0, out_device_ptrs=None, nt=None):
+        """An acquisition criterion over candidate points (gprhip_acquire): kind "ei" | "log_ei" | "pi" | "bound" (or a
+        GPRHIP_ACQ_* number), every one "larger is better"; maximise: larger targets are better.  best / xi: incumbent and
+        margin of ei, log_ei, pi; kappa: weight of the standard deviation in bound.  The criterion sees the variance
+        max(variance, var_floor) -- default 1e-10 sf2, the level of the variance's own error -- with sigma2 added when
+        `predictive`.  Returns a dict with the names in `want` -- values / means / variances [nt], dvalues D x nt in the layout
+        of the test inputs -- and, with top_k > 0 (at most 64), top_index [top_k] (the best candidates, value descending, the
+        lower index first among equal values, -1 where fewer qualify), top_values [top_k] and top_dvalues D x top_k (NaN
+        where top_index is -1).  want=() with top_k > 0 moves nothing of size nt off the device.
+        out_device_ptrs: {name: device address} for the names in `want` (vectors: nt doubles, dvalues point-major [nt][D]);
+        `test_inputs` is then the device address of a contiguous point-major [nt][D] fp64 array of `nt` points; only the
+        top_* entries are returned."""
+        want = tuple(want)
+        unknown = [w for w in want if w not in self.ACQUIRE_OUTPUTS]
+        if unknown:
+            raise ValueError("acquire: unknown outputs %s" % unknown)
+        if isinstance(kind, str):
+            if kind not in self.ACQUIRE_KINDS:
+                raise ValueError("acquire: unknown kind %r (one of %s)" % (kind, sorted(self.ACQUIRE_KINDS)))
+            kind = self.ACQUIRE_KINDS[kind]
+        if var_floor is None:
+            if getattr(self, "_log_sf2", None) is None:
+                raise ValueError("acquire: var_floor is needed (this object has not seen the model state's log_sf2)")
+            var_floor = 1e-10 * float(np.exp(self._log_sf2))
+        acq = _lib.Acquisition(int(kind), int(bool(maximise)), int(bool(predictive)), float(best), float(xi), float(kappa),
+                               float(var_floor))
+        top_k = int(top_k)
+        out = {}
+        kk = max(top_k, 1)
+        top_index = np.full(kk, -1, dtype=np.int64)
+        top_values = np.full(kk, np.nan, dtype=np.float64)
+        top_dvalues = np.full((self.D, kk), np.nan, dtype=np.float64, order="F")
+        tops = ((top_index.ctypes.data_as(C.POINTER(C.c_int64)), _f64_ptr(top_values), _f64_ptr(top_dvalues)) if top_k > 0
+                else (None, None, None))
+        null = C.c_void_p(None)
+        if out_device_ptrs is not None:
+            if nt is None:
+                raise ValueError("acquire: device buffers need nt")
+            ptrs = {w: (C.c_void_p(int(out_device_ptrs[w])) if w in want else null) for w in self.ACQUIRE_OUTPUTS}
+            xt_ptr, on_device = C.c_void_p(int(test_inputs)), 1
+            nt = int(nt)
+        else:
+            xt = np.asfortranarray(test_inputs, dtype=np.float64)
+            if xt.ndim != 2 or xt.shape[0] != self.D:
+                raise ValueError("acquire: expected test inputs of shape (%d, nt)" % self.D)
+            nt = xt.shape[1]
+            for w in want:
+                out[w] = (np.full((self.D, nt), np.nan, dtype=np.float64, order="F") if w == "dvalues"
+                          else np.empty(nt, dtype=np.float64))
+            ptrs = {w: (C.c_void_p(out[w].ctypes.data) if w in out else null) for w in self.ACQUIRE_OUTPUTS}
+            xt_ptr, on_device = C.c_void_p(xt.ctypes.data), 0
+        _lib.check(self._lib.gprhip_acquire(self._handle(), C.byref(acq), xt_ptr, self.D, nt, ptrs["values"], ptrs["dvalues"],
+                                            self.D, ptrs["means"], ptrs["variances"], top_k, *tops, on_device))
+        if top_k > 0:
+            out.update(top_index=top_index, top_values=top_values, top_dvalues=top_dvalues)
+        return out
+
     def train_stats(self, want_means=False):
         """Residual sums of the training set under the last evaluation's mean coefficients
         (Trained.calc_means + the loops of Stats.calc, lib/fitc_gp.ml:296-297, :353-373).
@@ -325,6 +389,7 @@ class Problem:
                        log_multiscales_m05=None):
         """Mean_predictor.calc / Co_variance_predictor.calc (lib/fitc_gp.ml:386-391, :446-447): install a saved
         model's predictor state; `predict` / `covariances` then work without any evaluation."""
+        self._log_sf2 = float(log_sf2)  # (Problem.acquire's default var_floor)
         h, keep = self._hypers(log_ell, log_sf2, sigma2, inducing, tproj, False, False, jitter,
                                log_hetero_skedasticity, log_multiscales_m05)
         c = u = r = None
@@ -353,6 +418,7 @@ class Problem:
     def eval_pass1(self, ar1_ptr, n_total, *, log_sf2, sigma2, inducing, log_ell=0.0, tproj=None,
                    variational=False, model_only=False, want_grad=True, jitter=CHOLESKY_JITTER,
                    log_hetero_skedasticity=None, log_multiscales_m05=None, reuse_v=False):
+        self._log_sf2 = float(log_sf2)  # (Problem.acquire's default var_floor)
         h, keep = self._hypers(log_ell, log_sf2, sigma2, inducing, tproj, variational, model_only, jitter,
                                log_hetero_skedasticity, log_multiscales_m05, reuse_v)
         self._has_ms = log_multiscales_m05 is not None

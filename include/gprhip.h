@@ -358,6 +358,54 @@ int gprhip_predict_input_grad(gprhip_problem* p, const double* test_inputs, int6
                               double* means, double* variances, double* dmeans, double* dvariances, int64_t ldg,
                               int on_device);
 
+/* An acquisition criterion over candidate points, with its gradient with respect to them and the best top_k candidates --
+ * the scoring phase of Bayesian optimisation or active learning, built on the posterior and its input gradients above (an
+ * extension beyond the reference's implemented surface).  Every criterion is "larger is better".  With mu_r / sigma2_r the mean
+ * and variance of gprhip_predict_input_grad at candidate r (sigma2 added when `predictive`),
+ *   s = +1 if maximise else -1,  v = max(sigma2_r, var_floor),  sigma = sqrt(v),  delta = s (mu_r - best) - xi,  u = delta / sigma,
+ *   Phi / phi the standard normal cdf / pdf,  h(u) = phi(u) + u Phi(u):
+ *   kind      value a                              c_mu = da/dmu                   c_v = da/dsigma2
+ *   EI        delta Phi(u) + sigma phi(u)          s Phi(u)                        phi(u) / (2 sigma)
+ *   LOG_EI    log sigma + log h(u)                 s Phi(u) / (sigma h(u))         phi(u) / (2 v h(u))
+ *   PI        Phi(u)                               s phi(u) / sigma                -u phi(u) / (2 v)
+ *   BOUND     s mu + kappa sigma                   s                               kappa / (2 sigma)
+ * values[r] = a, dvalues[:, r] = c_mu dmeans[:, r] + c_v dvariances[:, r] with the two gradients of
+ * gprhip_predict_input_grad; c_v = 0 where the variance was clamped (sigma2_r < var_floor).  Phi keeps its relative accuracy
+ * in the lower tail, and LOG_EI stays finite and accurate where EI underflows (u < -38).  means / variances are those of
+ * gprhip_predict_input_grad (the variance before the clamp).  BOUND with kappa == 0 and variances == NULL runs the mean part
+ * alone: neither M nor G is formed.
+ *   on_device = 0: test_inputs (Fortran D x nt, ld >= D), values / means / variances (nt) and dvalues (Fortran D x nt,
+ *                  ldg >= D, rows D..ldg-1 left untouched) are host buffers.
+ *   on_device = 1: they are device pointers on the problem's device, inputs and gradient point-major [nt][D], ld == ldg == D.
+ * Each of the four may be NULL.
+ * top_k > 0: top_index[0 .. top_k) (HOST, always) receives the indices of the top_k largest values over all nt candidates,
+ * value descending, the lower index first among equal values; NaN values are never selected.  top_values (top_k, may be
+ * NULL) and top_dvalues (D x top_k, leading dimension D, may be NULL) receive the value and the gradient at each.  Where
+ * fewer than top_k candidates qualify the remaining top_index entries are -1 and their top_values / top_dvalues are left
+ * untouched.  The selection runs on the device without atomics (two runs give the same bits); with values, dvalues, means
+ * and variances all NULL nothing of size nt leaves the device.
+ * GPRHIP_EBADARG: an unknown kind, xi < 0, kappa < 0, var_floor not positive and finite, a non-finite best, top_k outside
+ * 0 .. GPRHIP_MAX_TOP_K, top_k > 0 without top_index, nothing requested (the four outputs NULL and top_k == 0), bad ld / ldg.
+ * State and limits: as gprhip_predict_input_grad -- GPRHIP_ESTATE without a completed evaluation or a loaded predictor, on a
+ * loaded predictor without factors (unless the mean part alone runs), and after gprhip_eval_targets; the fp32-bulk
+ * coefficient guard applies; fp64 problems, one device, no multiscales, at most 64 point dimensions on the kernel side.  A
+ * refused call enqueues nothing and leaves the state valid; the call never changes the predictor state.
+ * Stage timers: those of gprhip_predict_input_grad, and per chunk "acq_select" (the selection). */
+enum { GPRHIP_ACQ_EI = 0, GPRHIP_ACQ_LOG_EI = 1, GPRHIP_ACQ_PI = 2, GPRHIP_ACQ_BOUND = 3 };
+#define GPRHIP_MAX_TOP_K 64
+typedef struct {
+  int kind;          /* one of GPRHIP_ACQ_* */
+  int maximise;      /* 1: larger targets are better; 0: smaller */
+  int predictive;    /* as gprhip_predict: add sigma2 to the variance the criterion sees */
+  double best;       /* incumbent f* (EI, LOG_EI, PI) */
+  double xi;         /* margin >= 0 (EI, LOG_EI, PI) */
+  double kappa;      /* >= 0 (BOUND) */
+  double var_floor;  /* > 0, finite: the criterion sees v = max(variance, var_floor) */
+} gprhip_acquisition;
+int gprhip_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const double* test_inputs, int64_t ld, int64_t nt,
+                   double* values, double* dvalues, int64_t ldg, double* means, double* variances, int top_k,
+                   int64_t* top_index, double* top_values, double* top_dvalues, int on_device);
+
 /* Training-set residual statistics with the model state left by the last evaluation (which must have had
  * targets): means[i] = K_nm[i,:] . coeffs over the resident training inputs (Trained.calc_means,
  * lib/fitc_gp.ml:296-297; host, n doubles, may be NULL) and

@@ -716,6 +716,27 @@ struct Make_deriv {
         return out;
       }
     };
+    // An acquisition criterion over the test inputs with its D x nt gradient and the best top_k candidates (gprhip_acquire:
+    // an extension beyond the reference's implemented surface).  top_index holds -1 where fewer than top_k qualify.
+    struct Acquired_t {
+      Vec values;
+      Mat dvalues;
+      std::vector<int64_t> top_index;
+      Vec top_values;
+      Mat top_dvalues;
+    };
+    struct Acquisition {
+      static Acquired_t calc(const Trained_t& trained, const Inputs_t& in, const gprhip_acquisition& acq, int top_k = 0) {
+        Problem& p = problem_for(trained, in, "Acquisition.calc");
+        const int k = top_k > 0 ? top_k : 0;
+        Acquired_t a{Vec((size_t)in.points->cols), Mat(in.points->rows, in.points->cols), std::vector<int64_t>((size_t)k, -1),
+                     Vec((size_t)k), Mat(in.points->rows, k > 0 ? k : 1)};
+        check(gprhip_acquire(p.get(), &acq, in.points->data(), in.points->rows, in.points->cols, a.values.data(),
+                             a.dvalues.data(), in.points->rows, nullptr, nullptr, top_k, k ? a.top_index.data() : nullptr,
+                             k ? a.top_values.data() : nullptr, k ? a.top_dvalues.data() : nullptr, 0));
+        return a;
+      }
+    };
     struct Covariances {  // FITC_covariances / FIC_covariances, :565-627
       template <class Owner>
       static Covariances_t calc(const Owner& cvp, double sigma2, const Inputs_t& in) {
