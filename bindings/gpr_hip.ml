@@ -54,6 +54,9 @@ external predict_input_grad : problem -> mat -> mat option -> mat option -> unit
 (* an acquisition criterion over the points and its gradient with respect to them (gprhip_acquire); the vector is
    [| kind; maximise; predictive; best; xi; kappa; var_floor |], kind 0 EI, 1 log EI, 2 PI, 3 bound *)
 external acquire : problem -> vec -> mat -> vec option -> mat option -> unit = "gprhip_ml_acquire"
+(* posterior sample paths (gprhip_sample_paths): z (m x ns normal draws) -> points -> eps (nt x ns, or None: the path part
+   alone) -> samples (nt x ns) *)
+external sample_paths : problem -> mat -> mat -> mat option -> mat -> unit = "gprhip_ml_sample_paths"
 external train_stats : problem -> vec option -> vec -> unit = "gprhip_ml_train_stats"
 external covariances : problem -> mat -> int -> bool -> mat -> unit = "gprhip_ml_covariances"
 external cov_samples : problem -> mat -> float -> float -> vec -> mat -> mat -> unit
@@ -661,6 +664,29 @@ module Make_variant
         res
 
       let sample ?rng t = Mat.col (samples ?rng t ~n:1) 1
+    end
+
+    (* Draws of the posterior as functions (an extension beyond the reference's signature): a sampler keeps its m x n normal
+       draws, so the same sampler evaluates the same n functions at any inputs; O(nt m) instead of Cov_sampler's nt x nt
+       factorisation.  At most 64 draws, fp64 problems, no multiscales. *)
+    module Path_sampler = struct
+      type t = { trained : Trained.t; z : mat }
+
+      let calc ?(rng = Gpr.Utils.default_rng) (trained : Trained.t) ~n =
+        let m = Mat.dim2 trained.Trained.model.Model.inputs.Inputs.inducing.Inducing.points in
+        { trained; z = Mat.init_cols m n (fun _ _ -> Gsl.Randist.gaussian_ziggurat rng ~sigma:1.) }
+
+      let samples ?(rng = Gpr.Utils.default_rng) ?(residual = true) t (inputs : Inputs.t) =
+        same_inducing t.trained.Trained.model.Model.inputs.Inputs.inducing.Inducing.points
+          inputs.Inputs.inducing.Inducing.points "Path_sampler.samples";
+        Trained.ensure_state t.trained;
+        let nt = Spec.Inputs.get_n_points inputs.Inputs.points and n = Mat.dim2 t.z in
+        let eps =
+          if residual then Some (Mat.init_cols nt n (fun _ _ -> Gsl.Randist.gaussian_ziggurat rng ~sigma:1.)) else None
+        in
+        let res = Mat.create nt n in
+        sample_paths (Lazy.force t.trained.Trained.model.Model.inputs.Inputs.dev).first t.z inputs.Inputs.points eps res;
+        res
     end
   end
 

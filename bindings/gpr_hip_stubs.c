@@ -191,6 +191,30 @@ CAMLprim value gprhip_ml_acquire(value prob, value params, value points, value v
   CAMLreturn(Val_unit);
 }
 
+/* external sample_paths : problem -> z:mat -> points:mat -> eps:mat option -> samples:mat -> unit
+ *   posterior sample paths at the points (nt x ns): column j is the draw fixed by column j of z (m x ns standard normal
+ *   draws); with eps (nt x ns) the independent residual part is added, without it the path part alone is returned */
+CAMLprim value gprhip_ml_sample_paths(value prob, value z, value points, value eps, value samples) {
+  CAMLparam5(prob, z, points, eps, samples);
+  struct caml_ba_array* ba = Caml_ba_array_val(points);
+  struct caml_ba_array* bz = Caml_ba_array_val(z);
+  gprhip_problem* p = Problem_val(prob);
+  const double* x = (const double*)ba->data;
+  const double* zz = (const double*)bz->data;
+  int64_t ld = ba->dim[0], nt = ba->dim[1], ldz = bz->dim[0];
+  int ns = (int)bz->dim[1];
+  const double* e = (const double*)opt_data(eps);
+  double* out = (double*)Caml_ba_data_val(samples);
+  int status;
+  if (Caml_ba_array_val(samples)->dim[0] != nt || Caml_ba_array_val(samples)->dim[1] != ns)
+    caml_invalid_argument("Gpr_hip.sample_paths: samples must be nt x ns");
+  caml_release_runtime_system();
+  status = gprhip_sample_paths(p, zz, ldz, ns, x, ld, nt, e, nt, 0, out, nt, 1, 0, NULL, NULL, NULL, 0);
+  caml_acquire_runtime_system();
+  check(status);
+  CAMLreturn(Val_unit);
+}
+
 /* external train_stats : problem -> means:vec option -> sums:vec -> unit      sums = [sse; sum|e|; max|e|; sum y^2] */
 CAMLprim value gprhip_ml_train_stats(value prob, value means, value sums) {
   CAMLparam3(prob, means, sums);

@@ -96,6 +96,7 @@ class Acquisition(C.Structure):
 
 ACQ_EI, ACQ_LOG_EI, ACQ_PI, ACQ_BOUND = range(4)
 MAX_TOP_K = 64    # GPRHIP_MAX_TOP_K
+MAX_DRAWS = 64    # GPRHIP_MAX_DRAWS
 MAX_TARGETS = 16  # GPRHIP_MAX_TARGETS
 MAX_BATCH = 64    # GPRHIP_MAX_BATCH
 
@@ -133,6 +134,8 @@ SIGNATURES = {
     "gprhip_predict_input_grad": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, _vp, _vp, _vp, _vp, C.c_int64, C.c_int]),
     "gprhip_acquire": (C.c_int, [_vp, C.POINTER(Acquisition), _vp, C.c_int64, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, C.c_int,
                                  C.POINTER(C.c_int64), _dp, _dp, C.c_int]),
+    "gprhip_sample_paths": (C.c_int, [_vp, _dp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int, _vp, C.c_int64,
+                                      C.c_int, C.c_int, C.POINTER(C.c_int64), _dp, _dp, C.c_int]),
     "gprhip_predict_targets": (C.c_int, [_vp, _dp, C.c_int64, C.c_int64, _dp]),
     "gprhip_train_stats": (C.c_int, [_vp, _dp, _dp]),
     "gprhip_covariances": (C.c_int, [_vp, _dp, C.c_int64, C.c_int64, C.c_int, C.c_int, _dp]),

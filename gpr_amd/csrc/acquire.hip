@@ -52,14 +52,19 @@ __device__ __forceinline__ void sel_block_best(unsigned long long& k, int& i, un
   __syncthreads();
 }
 
-__global__ __launch_bounds__(256) void acq_select_slab_kernel(const double* __restrict__ values, int rows, int k,
-                                                               unsigned long long* __restrict__ ckey,
+// (blockIdx.y: the value column -- ldv doubles apart, its candidate lists gridDim.x * k entries apart; sign: +1 the largest,
+//  -1 the smallest)
+__global__ __launch_bounds__(256) void acq_select_slab_kernel(const double* __restrict__ values, int64_t ldv, double sign,
+                                                               int rows, int k, unsigned long long* __restrict__ ckey,
                                                                int* __restrict__ cidx) {
   __shared__ unsigned long long keys[SEL_SLAB];
   __shared__ unsigned long long wk[4];
   __shared__ int wi[4];
   const int tid = threadIdx.x, base = blockIdx.x * SEL_SLAB;
-  for (int i = tid; i < SEL_SLAB; i += 256) keys[i] = base + i < rows ? sel_key(values[base + i]) : 0ull;
+  values += (int64_t)blockIdx.y * ldv;
+  ckey += (int64_t)blockIdx.y * gridDim.x * k;
+  cidx += (int64_t)blockIdx.y * gridDim.x * k;
+  for (int i = tid; i < SEL_SLAB; i += 256) keys[i] = base + i < rows ? sel_key(sign * values[base + i]) : 0ull;
   __syncthreads();
   unsigned long long bk;
   int bi;
@@ -94,13 +99,17 @@ __global__ __launch_bounds__(256) void acq_select_slab_kernel(const double* __re
 // out: [k] indices (as doubles; -1: fewer than k values qualify) | [k] values | [k][D] gradient rows (grads null: not written)
 __global__ __launch_bounds__(256) void acq_select_merge_kernel(const unsigned long long* __restrict__ ckey,
                                                                 const int* __restrict__ cidx, int nslabs, int k,
-                                                                const double* __restrict__ values,
+                                                                const double* __restrict__ values, int64_t ldv,
                                                                 const double* __restrict__ grads, int D,
-                                                                double* __restrict__ out) {
+                                                                double* __restrict__ out, int64_t out_stride) {
   __shared__ unsigned long long wk[4];
   __shared__ int wi[4];
   __shared__ int sel[64];
   const int tid = threadIdx.x;
+  values += (int64_t)blockIdx.y * ldv;
+  ckey += (int64_t)blockIdx.y * nslabs * k;
+  cidx += (int64_t)blockIdx.y * nslabs * k;
+  out += (int64_t)blockIdx.y * out_stride;
   int head = 0;
   unsigned long long bk = tid < nslabs ? ckey[(int64_t)tid * k] : 0ull;
   for (int it = 0; it < k; ++it) {
@@ -139,8 +148,29 @@ void launch_acq_select(const AcqSelectArgs& a, hipStream_t s) {
   }
   unsigned long long* const ckey = static_cast<unsigned long long*>(a.scratch);
   int* const cidx = reinterpret_cast<int*>(ckey + (int64_t)ACQ_SELECT_MAX_SLABS * ACQ_MAX_TOP_K);
-  hipLaunchKernelGGL(acq_select_slab_kernel, dim3(nslabs), dim3(256), 0, s, a.values, a.rows, a.k, ckey, cidx);
-  hipLaunchKernelGGL(acq_select_merge_kernel, dim3(1), dim3(256), 0, s, ckey, cidx, nslabs, a.k, a.values, a.grads, a.D, a.out);
+  hipLaunchKernelGGL(acq_select_slab_kernel, dim3(nslabs), dim3(256), 0, s, a.values, (int64_t)0, 1.0, a.rows, a.k, ckey, cidx);
+  hipLaunchKernelGGL(acq_select_merge_kernel, dim3(1), dim3(256), 0, s, ckey, cidx, nslabs, a.k, a.values, (int64_t)0, a.grads,
+                     a.D, a.out, (int64_t)0);
+  GPR_HIP(hipGetLastError());
+}
+
+int64_t acq_select_many_scratch_bytes(int64_t rows, int k, int ncols) {
+  return ((rows + SEL_SLAB - 1) / SEL_SLAB) * (int64_t)k * ncols * 12;
+}
+
+void launch_acq_select_many(const AcqSelectManyArgs& a, hipStream_t s) {
+  const int nslabs = (a.rows + SEL_SLAB - 1) / SEL_SLAB;
+  if (a.rows <= 0 || a.k < 1 || a.k > ACQ_MAX_TOP_K || nslabs > ACQ_SELECT_MAX_SLABS || a.ncols < 1 || a.ldv < a.rows ||
+      a.out_stride < 2 * a.k) {
+    set_error("gprhip: the selection takes 1 .. 64 candidates out of at most 524288 values per column and launch");
+    throw HipFail{ST_BAD_ARG};
+  }
+  unsigned long long* const ckey = static_cast<unsigned long long*>(a.scratch);
+  int* const cidx = reinterpret_cast<int*>(ckey + (int64_t)nslabs * a.k * a.ncols);
+  hipLaunchKernelGGL(acq_select_slab_kernel, dim3(nslabs, a.ncols), dim3(256), 0, s, a.values, a.ldv, a.sign, a.rows, a.k, ckey,
+                     cidx);
+  hipLaunchKernelGGL(acq_select_merge_kernel, dim3(1, a.ncols), dim3(256), 0, s, ckey, cidx, nslabs, a.k, a.values, a.ldv,
+                     static_cast<const double*>(nullptr), 0, a.out, a.out_stride);
   GPR_HIP(hipGetLastError());
 }
 

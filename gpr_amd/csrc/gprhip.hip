@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "mfma_gemm.h"
 #include "problem_internal.h"
+#include "sample_paths_host.h"
 
 namespace gprhip {
 const std::string& last_error();
@@ -280,6 +281,15 @@ struct gprhip_problem {
   // device and its pinned mirror; made at the first call with top_k > 0
   void* acq_scratch = nullptr;
   double *acq_out = nullptr, *acq_host = nullptr;
+  // gprhip_sample_paths: the normal draws Z [mp][64] in pinned host memory that the weight kernel reads, R~^-1 Z and the
+  // weights A (2 [mp][64]); F / eps of one chunk ([64][sp_rows] each, made when a call needs them); the selection's
+  // candidate lists and the winners' blocks [64][64 (D + 2)] with their pinned mirror
+  double *sp_zhost = nullptr, *sp_coef = nullptr;
+  double *sp_f = nullptr, *sp_eps = nullptr;
+  int64_t sp_f_rows = 0, sp_eps_rows = 0;
+  void* sp_scratch = nullptr;
+  int64_t sp_scratch_bytes = 0;
+  double *sp_out = nullptr, *sp_host = nullptr;
   bool use_small() const {
     return !multi && !xg_engine && small_path && !f32 && !engine_steps && small_path_fits(m, mp, d, has_proj() ? D : 0, n, has_ms());
   }
@@ -2019,7 +2029,9 @@ struct PgPlan {
   double *bufA, *bufB;              // K and G of a chunk
   double *rmean, *rvar, *rval;      // three row vectors of xt_rows entries
 };
-PgPlan pg_prepare(gprhip_problem* p, const char* fn, int64_t nt, bool want_var, bool host_g) {
+// with_pg = false (gprhip_sample_paths): neither M nor the gradient staging is made -- K and K U^-1 of a chunk are all it needs
+PgPlan pg_prepare(gprhip_problem* p, const char* fn, int64_t nt, bool want_var, bool host_g, bool with_pg = true,
+                  int64_t extra_bytes = 0) {
   hipStream_t s = p->stream;
   const int mp = p->mp, D = p->D, d = p->d;
   const bool proj = p->has_proj();
@@ -2039,13 +2051,13 @@ PgPlan pg_prepare(gprhip_problem* p, const char* fn, int64_t nt, bool want_var, 
     }
   }
   // everything this call allocates, after a look at the device's free memory: a refusal leaves the problem as it was
-  const bool need_m = mats && !p->pg_m;
+  const bool need_m = mats && with_pg && !p->pg_m;
   const bool grow_xt = !(p->xt && p->xt_rows >= chunk);
-  const bool grow_pg = (host_g || proj) && (p->pg_rows < chunk || (host_g && !p->pg_host) || (proj && !p->pg_proj));
+  const bool grow_pg = with_pg && (host_g || proj) && (p->pg_rows < chunk || (host_g && !p->pg_host) || (proj && !p->pg_proj));
   const bool pg_host = host_g || p->pg_host, pg_proj = proj || p->pg_proj;
   const int64_t pg_len = 2 * chunk * ((pg_host ? D : 0) + (pg_proj ? d : 0));
   {
-    int64_t need = 0;
+    int64_t need = extra_bytes;
     if (need_m) need += (int64_t)mp * mp * 8;
     if (grow_pred) need += 2 * chunk * mp * 8;
     if (grow_xt) need += chunk * (D + d + 3) * 8;
@@ -2353,6 +2365,191 @@ void do_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const double* 
     if (top_values) top_values[j] = best_val[j];
     if (top_dvalues) std::copy(best_grad.begin() + (size_t)j * D, best_grad.begin() + (size_t)(j + 1) * D, top_dvalues + (int64_t)j * D);
   }
+  if (p->timer.on) tcollect(p);
+}
+
+// gprhip_sample_paths: ns draws of the posterior as functions, evaluated at nt test points chunk by chunk with do_predict's
+// chunk rule (sample_paths.hip).  The weights A = t 1^T + U^-1 (R~^-1 Z) are formed once per call; per chunk one kernel gives
+// F = K A (draw-major; K never reaches memory), with eps the residual standard deviation sqrt(max(0, sf2 - |K_r U^-1|^2 (+
+// sigma2))) eps is added in place, the best top_k of every draw are selected on the device (acquire.hip, one launch pair for
+// all draws), the path gradient is evaluated at them, and the chunks' lists are merged here (sample_paths_host.h).
+// The caller has checked the arguments.  The model state is read only: pg_m is neither needed nor touched.
+void do_sample_paths(gprhip_problem* p, const double* z, int64_t ldz, int ns, const double* test_inputs, int64_t ld, int64_t nt,
+                     const double* eps, int64_t lde, int predictive, double* samples, int64_t lds, int maximise, int top_k,
+                     int64_t* top_index, double* top_values, double* top_dvalues, int on_device) {
+  if (!p->have_model || p->stage != 0) {
+    set_error("gprhip_sample_paths: no completed evaluation to draw from");
+    throw HipFail{ST_STATE};
+  }
+  if (p->has_ms()) {
+    set_error("gprhip_sample_paths: multiscales are not supported (the model state has log_multiscales_m05)");
+    throw HipFail{ST_BAD_ARG};
+  }
+  if (!p->have_factors) {
+    set_error("gprhip_sample_paths: the loaded predictor has no co-variance coefficients (chol_km, r_mat)");
+    throw HipFail{ST_STATE};
+  }
+  if (p->multi_state) {
+    set_error("gprhip_sample_paths: the last evaluation was gprhip_eval_targets (several target vectors): draws are "
+              "available after the next gprhip_eval");
+    throw HipFail{ST_STATE};
+  }
+  need_trustworthy_coeffs(p, "gprhip_sample_paths");
+  GPR_HIP(hipSetDevice(p->device));
+  hipStream_t s = p->stream;
+  const int mp = p->mp, m = p->m, D = p->D, d = p->d;
+  const bool resid = eps != nullptr;
+  const bool stage_f = !(on_device && samples), stage_e = resid && !on_device;
+  // this call's own buffers, as far as they must grow: counted before anything is allocated (an upper bound on the rows of
+  // a chunk is enough for that)
+  const int64_t rows_cap = std::min<int64_t>(round_up(nt, TILE), std::max<int64_t>({131072, p->chunk, p->xt_rows, p->pred_rows}));
+  const int64_t piece_rows = (int64_t)ACQ_SELECT_MAX_SLABS * 2048;
+  const int64_t out_stride = (int64_t)top_k * (D + 2);
+  int64_t extra = 0;
+  if (!p->sp_coef) extra += 2 * (int64_t)mp * SP_MAX_DRAWS * 8;
+  if (stage_f && p->sp_f_rows < ns * rows_cap) extra += ns * rows_cap * 8;
+  if (stage_e && p->sp_eps_rows < ns * rows_cap) extra += ns * rows_cap * 8;
+  if (top_k > 0) {
+    extra += std::max<int64_t>(0, acq_select_many_scratch_bytes(std::min(rows_cap, piece_rows), top_k, ns) - p->sp_scratch_bytes);
+    if (!p->sp_out) extra += (int64_t)SP_MAX_DRAWS * ACQ_MAX_TOP_K * (D + 2) * 8;
+  }
+  const PgPlan plan = pg_prepare(p, "gprhip_sample_paths", nt, resid, false, false, extra);
+  const int64_t chunk = plan.chunk;
+  const int64_t rows_need = std::min<int64_t>(chunk, round_up(nt, TILE));  // rows of a chunk of this call
+  // (the pinned buffer first: a failure leaves both pointers null.  The weight kernel reads it by its host address, as
+  //  ship_kernel writes res_host: mapped, portable pinned memory has one address on host and device here)
+  if (!p->sp_zhost)
+    GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->sp_zhost), (size_t)mp * SP_MAX_DRAWS * sizeof(double),
+                          hipHostMallocPortable | hipHostMallocMapped));
+  if (!p->sp_coef) p->sp_coef = p->alloc<double>(2 * (int64_t)mp * SP_MAX_DRAWS);
+  if (stage_f && p->sp_f_rows < ns * rows_need) {
+    GPR_HIP(hipStreamSynchronize(s));
+    release_buf(p, p->sp_f);
+    p->sp_f_rows = 0;
+    p->sp_f = p->alloc<double>(ns * rows_need);
+    p->sp_f_rows = ns * rows_need;
+  }
+  if (stage_e && p->sp_eps_rows < ns * rows_need) {
+    GPR_HIP(hipStreamSynchronize(s));
+    release_buf(p, p->sp_eps);
+    p->sp_eps_rows = 0;
+    p->sp_eps = p->alloc<double>(ns * rows_need);
+    p->sp_eps_rows = ns * rows_need;
+  }
+  if (top_k > 0) {
+    const int64_t need = acq_select_many_scratch_bytes(std::min(rows_need, piece_rows), top_k, ns);
+    if (p->sp_scratch_bytes < need) {
+      GPR_HIP(hipStreamSynchronize(s));
+      release_buf(p, p->sp_scratch);
+      p->sp_scratch_bytes = 0;
+      p->sp_scratch = p->alloc<char>(need);
+      p->sp_scratch_bytes = need;
+    }
+    if (!p->sp_out) {
+      const int64_t len = (int64_t)SP_MAX_DRAWS * ACQ_MAX_TOP_K * (D + 2);
+      p->sp_out = p->alloc<double>(len);
+      GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->sp_host), (size_t)len * sizeof(double), hipHostMallocDefault));
+    }
+  }
+  // the weights, once per call: R~^-1 Z first, then U^-1 times it, plus t
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j < ns; ++j) p->sp_zhost[(int64_t)i * SP_MAX_DRAWS + j] = z[(int64_t)j * ldz + i];
+  double* const w1 = p->sp_coef;
+  double* const wA = p->sp_coef + (int64_t)mp * SP_MAX_DRAWS;
+  tstart(p, "sp_coeff");
+  launch_sp_weights(p->rinv, p->uinv, p->sp_zhost, p->tvec, m, mp, ns, w1, wA, s);
+  tstop(p);
+  const double add = predictive ? p->h.sigma2 : 0.0;
+  const double sign = maximise ? 1.0 : -1.0;
+  const bool want_g = top_k > 0 && top_dvalues;
+  std::vector<SpBest> best(top_k > 0 ? ns : 0);
+  for (int64_t lo = 0; lo < nt; lo += chunk) {
+    const int rows = (int)std::min<int64_t>(chunk, nt - lo);
+    const int rows_p = (int)round_up(rows, TILE);
+    const double* xin = test_inputs + lo * D;
+    if (!on_device) {
+      GPR_HIP(hipMemcpy2DAsync(p->xt, (size_t)D * sizeof(double), test_inputs + lo * ld, (size_t)ld * sizeof(double),
+                               (size_t)D * sizeof(double), (size_t)rows, hipMemcpyHostToDevice, s));
+      xin = p->xt;
+    }
+    const double* pts = xin;
+    if (plan.proj) {
+      launch_project(xin, rows, D, d, p->tproj, p->pt, s);
+      pts = p->pt;
+    }
+    double* const Fd = stage_f ? p->sp_f : samples + lo;
+    const int64_t ldf = stage_f ? rows_need : lds;
+    tstart(p, "sp_path");
+    SamplePathArgs a;
+    a.pts = pts; a.Z = p->Z; a.shift = p->zshift; a.W = wA; a.ldw = SP_MAX_DRAWS; a.ns = ns;
+    a.rows = rows; a.m = m; a.d = d; a.log_sf2 = p->cp.log_sf2; a.inv_ell2_05 = p->cp.inv_ell2_05;
+    a.F = Fd; a.ldf = ldf; a.sumsq = nullptr;
+    launch_sample_paths(a, s);
+    tstop(p);
+    if (resid) {
+      const double* E = eps + lo;
+      int64_t ldE = lde;
+      if (!on_device) {
+        GPR_HIP(hipMemcpy2DAsync(p->sp_eps, (size_t)rows_need * sizeof(double), eps + lo, (size_t)lde * sizeof(double),
+                                 (size_t)rows * sizeof(double), (size_t)ns, hipMemcpyHostToDevice, s));
+        E = p->sp_eps;
+        ldE = rows_need;
+      }
+      tstart(p, "sp_resid");
+      if (plan.small) {  // few inducing points: |K_r U^-1|^2 in one kernel, no chunk x mp matrix
+        SamplePathArgs r = a;
+        r.W = p->uinv; r.ldw = mp; r.ns = m; r.F = nullptr; r.sumsq = plan.rvar;
+        launch_sp_row_sumsq(r, s);
+      } else {
+        launch_cov_cross<double>(p->cp, pts, rows, rows_p, p->Z, m, mp, d, plan.bufA, s);
+        GemmArgs g;  // V = K U^-1
+        g.A = plan.bufA; g.lda = mp; g.B = p->uinv; g.ldb = mp; g.C = plan.bufB; g.ldc = mp;
+        g.M = rows_p; g.N = mp; g.K = mp; g.tri = TRI_KHI_BN;
+        launch_gemm(OP_NN, g, s);
+        launch_row_sumsq_dot<double>(plan.bufB, nullptr, rows, mp, plan.rvar, nullptr, s);
+      }
+      launch_sp_combine(Fd, ldf, E, ldE, plan.rvar, p->cp.sf2, add, rows, ns, s);
+      tstop(p);
+    }
+    if (!on_device && samples)
+      GPR_HIP(hipMemcpy2DAsync(samples + lo, (size_t)lds * sizeof(double), Fd, (size_t)ldf * sizeof(double),
+                               (size_t)rows * sizeof(double), (size_t)ns, hipMemcpyDeviceToHost, s));
+    // the best top_k of every draw over the chunk, in pieces of at most 256 slabs, before its buffers are reused
+    for (int64_t po = 0; top_k > 0 && po < rows; po += piece_rows) {
+      const int pr = (int)std::min<int64_t>(piece_rows, rows - po);
+      tstart(p, "sp_select");
+      AcqSelectManyArgs sel;
+      sel.values = Fd + po; sel.ldv = ldf; sel.rows = pr; sel.k = top_k; sel.ncols = ns; sel.sign = sign;
+      sel.scratch = p->sp_scratch; sel.out = p->sp_out; sel.out_stride = out_stride;
+      launch_acq_select_many(sel, s);
+      if (want_g) {
+        PathGradAtArgs g;
+        g.pts = pts + po * d; g.Z = p->Z; g.shift = p->zshift; g.W = wA; g.tproj = plan.proj ? p->tproj : nullptr;
+        g.rows = pr; g.m = m; g.d = d; g.D = D; g.k = top_k; g.ns = ns;
+        g.log_sf2 = p->cp.log_sf2; g.inv_ell2_05 = p->cp.inv_ell2_05; g.out = p->sp_out; g.out_stride = out_stride;
+        launch_path_grad_at(g, s);
+      }
+      tstop(p);
+      GPR_HIP(hipMemcpyAsync(p->sp_host, p->sp_out, (size_t)(ns * out_stride) * sizeof(double), hipMemcpyDeviceToHost, s));
+      GPR_HIP(hipStreamSynchronize(s));
+      for (int j = 0; j < ns; ++j) {
+        const double* const blk = p->sp_host + (int64_t)j * out_stride;
+        sp_merge_topk(best[j], top_k, sign, blk, blk + top_k, want_g ? blk + 2 * top_k : nullptr, D, lo + po);
+      }
+    }
+    GPR_HIP(hipStreamSynchronize(s));  // the chunk buffers are reused by the next chunk; device outputs are complete
+  }
+  for (int j = 0; j < ns && top_k > 0; ++j)
+    for (int i = 0; i < top_k; ++i) {
+      const int64_t e = (int64_t)j * top_k + i;
+      if (i >= (int)best[j].idx.size()) {
+        top_index[e] = -1;  // fewer than top_k points qualify: their values and gradients are left as they are
+        continue;
+      }
+      top_index[e] = best[j].idx[i];
+      if (top_values) top_values[e] = best[j].val[i];
+      if (top_dvalues) std::copy(best[j].grad.begin() + (size_t)i * D, best[j].grad.begin() + (size_t)(i + 1) * D, top_dvalues + e * D);
+    }
   if (p->timer.on) tcollect(p);
 }
 
@@ -3145,6 +3342,8 @@ void gprhip_problem_destroy(gprhip_problem* p) {
   if (p->hy_host && !p->is_lane) hipHostFree(p->hy_host);
   if (p->res_host) hipHostFree(p->res_host);
   if (p->acq_host) hipHostFree(p->acq_host);
+  if (p->sp_zhost) hipHostFree(p->sp_zhost);
+  if (p->sp_host) hipHostFree(p->sp_host);
   if (p->ev_fork) hipEventDestroy(p->ev_fork);
   if (p->ev_join) hipEventDestroy(p->ev_join);
   if (p->ev_rf) hipEventDestroy(p->ev_rf);
@@ -3645,6 +3844,26 @@ int gprhip_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const doubl
     }
     do_acquire(p, acq, test_inputs, ld, nt, values, dvalues, ldg, means, variances, top_k, top_index, top_values, top_dvalues,
                on_device);
+  }, p);
+}
+
+int gprhip_sample_paths(gprhip_problem* p, const double* z, int64_t ldz, int ns, const double* test_inputs, int64_t ld, int64_t nt,
+                        const double* eps, int64_t lde, int predictive, double* samples, int64_t lds, int maximise, int top_k,
+                        int64_t* top_index, double* top_values, double* top_dvalues, int on_device) {
+  return guarded([&] {
+    SpCall c;
+    c.have_p = p != nullptr;
+    if (p) {
+      c.D = p->D; c.d = p->d; c.m = p->m; c.f32 = p->f32;
+    }
+    c.z = z; c.ldz = ldz; c.ns = ns; c.test_inputs = test_inputs; c.ld = ld; c.nt = nt; c.eps = eps; c.lde = lde;
+    c.samples = samples; c.lds = lds; c.top_k = top_k; c.top_index = top_index; c.on_device = on_device;
+    if (const char* why = sp_check_args(c)) {
+      set_error(std::string("gprhip_sample_paths: ") + why);
+      throw HipFail{ST_BAD_ARG};
+    }
+    do_sample_paths(p, z, ldz, ns, test_inputs, ld, nt, eps, lde, predictive, samples, lds, maximise, top_k, top_index,
+                    top_values, top_dvalues, on_device);
   }, p);
 }
 

@@ -328,6 +328,59 @@ struct AcqSelectArgs {
 };
 int64_t acq_select_scratch_bytes();
 void launch_acq_select(const AcqSelectArgs& a, hipStream_t s);
+// the same pair of kernels over `ncols` value columns in one launch each (column = blockIdx.y): the k best of
+// sign * values[col * ldv + (0 .. rows)) per column, by the same rule; out + col * out_stride = [k] indices | [k] values (the
+// entries of `values`, unsigned) -- out_stride >= 2 k, what lies behind the values is not written
+struct AcqSelectManyArgs {
+  const double* values;  // [ncols][ldv]
+  int64_t ldv;
+  int rows, k, ncols;    // rows <= 2048 ACQ_SELECT_MAX_SLABS
+  double sign;           // +1: the largest, -1: the smallest
+  void* scratch;         // acq_select_many_scratch_bytes(rows, k, ncols)
+  double* out;
+  int64_t out_stride;
+};
+int64_t acq_select_many_scratch_bytes(int64_t rows, int k, int ncols);
+void launch_acq_select_many(const AcqSelectManyArgs& a, hipStream_t s);
+
+// ---- posterior sample paths (sample_paths.hip): a draw is f(x) = sum_c k(x, z_c) a_c with the weights a = t + U^-1 R~^-1 z
+constexpr int SP_MAX_DRAWS = 64;  // GPRHIP_MAX_DRAWS, and the leading dimension of the m x ns weight matrices ([mp][64])
+// the weights: w1 [mp][64] = Rinv Zh, out [mp][64] = tvec 1^T + Uinv w1 for upper-triangular row-major mp x mp factors and Zh
+// [mp][64] (rows < m, columns < ns read; device-visible); rows >= m and columns >= ns of w1 and out are zero
+void launch_sp_weights(const double* Rinv, const double* Uinv, const double* Zh, const double* tvec, int m, int mp, int ns,
+                       double* w1, double* out, hipStream_t s);
+struct SamplePathArgs {
+  const double* pts;     // [rows][d]  test points (iso) or their projections (fat)
+  const double* Z;       // [mp][d]
+  const double* shift;   // [d] common offset s (the centroid of the inducing points)
+  const double* W;       // weights: rows < m, columns < ns of a row-major matrix with leading dimension ldw
+  int64_t ldw;
+  int ns;                // 1 .. SP_MAX_DRAWS
+  int rows, m, d;        // d <= 64
+  double log_sf2, inv_ell2_05;
+  double* F;             // out, draw-major: F[j * ldf + r] = sum_c K_rc W_cj  (launch_sample_paths)
+  int64_t ldf;
+  double* sumsq;         // out [rows]: sum_j (K W)_rj^2  (launch_sp_row_sumsq)
+};
+void launch_sample_paths(const SamplePathArgs& a, hipStream_t s);
+// |K_r U^-1|^2 per test point for at most 64 inducing points of at most 16 dimensions (W = U^-1, ldw = mp, ns = m): no
+// chunk x mp matrix
+void launch_sp_row_sumsq(const SamplePathArgs& a, hipStream_t s);
+// F[j][r] += sqrt(max(0, (sf2 - sumsq[r]) + add)) eps[j][r]
+void launch_sp_combine(double* F, int64_t ldf, const double* eps, int64_t lde, const double* sumsq, double sf2, double add,
+                       int rows, int ns, hipStream_t s);
+// gradient of draw j at its k selected points: df_j/dp_r = -inv_ell2 sum_c K_rc W_cj (p_r - z_c), then tproj (D x d) times it
+struct PathGradAtArgs {
+  const double* pts;     // [rows][d] of the chunk
+  const double *Z, *shift;
+  const double* W;       // [mp][SP_MAX_DRAWS]
+  const double* tproj;   // as launch_project takes it, or null (then D == d)
+  int rows, m, d, D, k, ns;
+  double log_sf2, inv_ell2_05;
+  double* out;           // per draw: [k] indices (in, as doubles; -1: none) | [k] values | [k][D] gradients (out)
+  int64_t out_stride;
+};
+void launch_path_grad_at(const PathGradAtArgs& a, hipStream_t s);
 
 // ---- m x m finalisation (finalize.hip)
 // dst (upper tiles) = base + sum_z slices[z]; the diagonal tiles sum the first nslices_diag slices only (0 = nslices;

@@ -34,6 +34,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
+from . import _lib
 from .problem import CHOLESKY_JITTER, Problem
 
 
@@ -449,6 +450,40 @@ def _make_variant(spec, variational, functor, cov_kind="FITC"):
         return _problem_of(trained, inputs).acquire(inputs.points, kind, **kw)
 
     Eval.Acquisition = SimpleNamespace(calc=acquisition_calc)
+
+    # ---- posterior sample paths (gprhip_sample_paths through Problem.sample_paths: an extension beyond the reference's
+    # implemented surface, whose Cov_sampler factors an nt x nt covariance).  A sampler keeps its m x n normal draws: the same
+    # sampler evaluates the same n functions at any inputs.
+    class _PathSampler:
+        def __init__(self, trained, z):
+            self.trained, self.z = trained, z
+
+    def path_sampler_calc(trained, n, rng=None):
+        if not isinstance(trained, _Trained):
+            raise TypeError("Path_sampler.calc: a trained model (the object of Trained.calc) is needed")
+        if not 1 <= int(n) <= _lib.MAX_DRAWS:
+            raise ValueError("Path_sampler.calc: 1 .. %d draws" % _lib.MAX_DRAWS)
+        rng = np.random.default_rng() if rng is None else rng
+        m = trained.model.inputs.inducing.points.shape[1]
+        return _PathSampler(trained, np.asfortranarray(rng.standard_normal((m, int(n)))))
+
+    def path_sampler_samples(sampler, inputs, residual=True, rng=None, predictive=False):
+        """nt x n samples at the inputs: the path part, plus (residual) the independent part that completes the variance of
+        Variances.calc, with fresh normal draws from rng"""
+        eps = None
+        if residual:
+            rng = np.random.default_rng() if rng is None else rng
+            eps = np.asfortranarray(rng.standard_normal((inputs.points.shape[1], sampler.z.shape[1])))
+        return _problem_of(sampler.trained, inputs).sample_paths(inputs.points, sampler.z, eps=eps,
+                                                                 predictive=predictive)["samples"]
+
+    def path_sampler_best(sampler, inputs, k, maximise=True):
+        """per draw the k best inputs of the path part: dict(top_index k x n, top_values k x n, top_dvalues D x k x n)"""
+        return _problem_of(sampler.trained, inputs).sample_paths(inputs.points, sampler.z, maximise=maximise, top_k=k,
+                                                                 want_samples=False)
+
+    Eval.Path_sampler = SimpleNamespace(calc=path_sampler_calc, samples=path_sampler_samples, best=path_sampler_best,
+                                        get_draws=lambda sampler: sampler.z)
 
     # ---- single-point prediction (Input / Mean / Variance, lib/fitc_gp.ml:88-101, :402-414, :447-482)
     class _Input:

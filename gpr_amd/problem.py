@@ -336,6 +336,70 @@ class Problem:
             out.update(top_index=top_index, top_values=top_values, top_dvalues=top_dvalues)
         return out
 
+    def sample_paths(self, test_inputs, z, eps=None, predictive=False, maximise=True, top_k=0, want_samples=True,
+                     out_device_ptrs=None, nt=None):
+        """Posterior sample paths at test points (gprhip_sample_paths).  z: m x ns standard normal draws (host, 1 <= ns <= 64);
+        column j fixes the draw f_j(x) = sum_c k(x, z_c) a_cj, a_j = t + R^-1 z_j, a function that the same z evaluates again
+        at any other points.  eps: nt x ns standard normal draws, or None for the path part alone; with eps the sample adds
+        sqrt(max(0, sf2 - |K_r U^-1|^2 (+ sigma2 if predictive))) eps, so that mean and variance are those of `predict`.
+        Returns a dict: samples (nt x ns, unless want_samples is False) and, with top_k > 0 (at most 64), per draw top_index
+        (top_k x ns; the largest -- maximise=False: the smallest -- samples first, the lower index first among equal values,
+        -1 where fewer qualify), top_values (top_k x ns) and top_dvalues (D x top_k x ns: the gradient of the PATH part at each
+        winner; NaN where top_index is -1).  want_samples=False with top_k > 0 moves nothing of size nt off the device.
+        out_device_ptrs: {"samples": device address of [ns][nt] doubles} (or {} for the top_* entries alone); `test_inputs`
+        is then the device address of a contiguous point-major [nt][D] fp64 array, `nt` (required then, else not used) the
+        number of points, `eps` None or the device address (an int) of [ns][nt] doubles -- an array is refused --, and only
+        the top_* entries are returned.
+        fp64 problems, no multiscales, at most 64 point dimensions on the kernel side (the library refuses otherwise)."""
+        z = np.asfortranarray(z, dtype=np.float64)
+        if z.ndim == 1:
+            z = np.asfortranarray(z.reshape(-1, 1))
+        if z.ndim != 2 or z.shape[0] != self.m:
+            raise ValueError("sample_paths: expected z of shape (%d, ns)" % self.m)
+        ns = z.shape[1]
+        top_k = int(top_k)
+        kk = max(top_k, 1)
+        top_index = np.full((kk, max(ns, 1)), -1, dtype=np.int64, order="F")
+        top_values = np.full((kk, max(ns, 1)), np.nan, dtype=np.float64, order="F")
+        top_dvalues = np.full((self.D, kk, max(ns, 1)), np.nan, dtype=np.float64, order="F")
+        tops = ((top_index.ctypes.data_as(C.POINTER(C.c_int64)), _f64_ptr(top_values), _f64_ptr(top_dvalues)) if top_k > 0
+                else (None, None, None))
+        null = C.c_void_p(None)
+        out = {}
+        if out_device_ptrs is not None:
+            if nt is None:
+                raise ValueError("sample_paths: device buffers need nt")
+            nt = int(nt)
+            unknown = [w for w in out_device_ptrs if w != "samples"]
+            if unknown:
+                raise ValueError("sample_paths: unknown device outputs %s" % unknown)
+            if eps is not None and not isinstance(eps, (int, np.integer)):
+                raise TypeError("sample_paths: with device buffers eps is a device address (an int), not an array")
+            sp = C.c_void_p(int(out_device_ptrs["samples"])) if out_device_ptrs.get("samples") else null
+            ep = C.c_void_p(int(eps)) if eps is not None else null
+            xt_ptr, on_device = C.c_void_p(int(test_inputs)), 1
+        else:
+            xt = np.asfortranarray(test_inputs, dtype=np.float64)
+            if xt.ndim != 2 or xt.shape[0] != self.D:
+                raise ValueError("sample_paths: expected test inputs of shape (%d, nt)" % self.D)
+            nt = xt.shape[1]
+            if eps is not None:
+                eps = np.asfortranarray(eps, dtype=np.float64)
+                if eps.ndim == 1:
+                    eps = np.asfortranarray(eps.reshape(-1, 1))
+                if eps.shape != (nt, ns):
+                    raise ValueError("sample_paths: expected eps of shape (%d, %d)" % (nt, ns))
+            if want_samples:
+                out["samples"] = np.empty((nt, ns), dtype=np.float64, order="F")
+            sp = C.c_void_p(out["samples"].ctypes.data) if want_samples else null
+            ep = C.c_void_p(eps.ctypes.data) if eps is not None else null
+            xt_ptr, on_device = C.c_void_p(xt.ctypes.data), 0
+        _lib.check(self._lib.gprhip_sample_paths(self._handle(), _f64_ptr(z), self.m, ns, xt_ptr, self.D, nt, ep, nt,
+                                                 int(bool(predictive)), sp, nt, int(bool(maximise)), top_k, *tops, on_device))
+        if top_k > 0:
+            out.update(top_index=top_index, top_values=top_values, top_dvalues=top_dvalues)
+        return out
+
     def train_stats(self, want_means=False):
         """Residual sums of the training set under the last evaluation's mean coefficients
         (Trained.calc_means + the loops of Stats.calc, lib/fitc_gp.ml:296-297, :353-373).

@@ -406,6 +406,41 @@ int gprhip_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const doubl
                    double* values, double* dvalues, int64_t ldg, double* means, double* variances, int top_k,
                    int64_t* top_index, double* top_values, double* top_dvalues, int on_device);
 
+/* Posterior sample paths over test points, with the best top_k points of every draw -- Thompson sampling, batch selection by
+ * independent draws, posterior pictures over a grid (an extension beyond the reference's implemented surface; its Cov_sampler
+ * forms and factors an nt x nt covariance).  The FITC posterior is a Gaussian over m weights, so a draw is a FUNCTION of x,
+ * fixed by z and evaluable at any set of points for O(nt m):
+ *   a_j = t + U^-1 (R~^-1 z_j),  z_j ~ N(0, I_m)          (R = R~ U = r_mat: Cov a = R^-1 R^-T = B^-1, mean a = t = the mean coefficients)
+ *   f_j(x) = sum_c k(x, z_c) a_cj                          -- the path part
+ *   samples[r, j] = f_j(x_r) + sqrt(max(0, sf2 - |K_r U^-1|^2 (+ sigma2 if predictive))) eps[r, j],  eps ~ N(0, 1) independent
+ * Over z and eps the mean is gprhip_predict's mean, the variance exactly gprhip_predict's variance, and the covariance of
+ * two different points Q Q^T with Q = K_tm R^-1 -- the off-diagonal of gprhip_covariances kind 1: the posterior under the
+ * conditional independence FITC itself assumes.  The normal draws are the caller's (as with gprhip_cov_samples): the library
+ * stays deterministic.
+ *   z: HOST always, Fortran m x ns (ldz >= m), 1 <= ns <= GPRHIP_MAX_DRAWS.
+ *   eps: nt x ns (lde >= nt), or NULL: the path part only (`predictive` is then ignored).
+ *   samples: nt x ns (lds >= nt); may be NULL (with top_k > 0: nothing of size nt leaves the device).
+ *   on_device = 0: test_inputs (Fortran D x nt, ld >= D), eps and samples (Fortran nt x ns) are host buffers.
+ *   on_device = 1: device pointers on the problem's device: test_inputs point-major [nt][D] (ld == D), eps / samples
+ *                  draw-major [ns][lde] / [ns][lds] -- the same memory layout.
+ * top_k > 0: per draw j, top_index[j * top_k + (0 .. top_k)) (HOST, always) receives the indices of the top_k largest
+ * (maximise = 0: smallest) entries of samples[:, j], best first, the lower index first among equal values; NaN is never
+ * selected; where fewer qualify the remaining indices are -1 and their values / gradients are left untouched.  top_values
+ * (HOST, top_k x ns, may be NULL) receives the entries themselves, top_dvalues (HOST, D x top_k x ns, may be NULL) the
+ * gradient of the PATH part f_j with respect to the test input at each winner.  The selection runs on the device without
+ * atomics: two runs give the same bits.
+ * GPRHIP_EBADARG: ns outside 1 .. GPRHIP_MAX_DRAWS, top_k outside 0 .. GPRHIP_MAX_TOP_K, top_k > 0 without top_index, nothing
+ * requested (samples NULL and top_k == 0), bad ldz / ld / lde / lds, an fp32-bulk problem, a model state with multiscales,
+ * more than 64 point dimensions on the kernel side.  GPRHIP_ESTATE: no completed evaluation or loaded predictor, a predictor
+ * loaded without factors, after gprhip_eval_targets.  The fp32-bulk coefficient guard applies.  New buffers are checked against
+ * the free device memory first (GPRHIP_EOOM).  A refused call enqueues nothing; the call never changes the predictor state.
+ * Stage timers: "sp_coeff" (the weights, once per call), and per chunk "sp_path" (F = K A, K recomputed on the fly),
+ * "sp_resid" (with eps: the residual standard deviation and its addition), "sp_select" (selection and the winners' gradients). */
+#define GPRHIP_MAX_DRAWS 64
+int gprhip_sample_paths(gprhip_problem* p, const double* z, int64_t ldz, int ns, const double* test_inputs, int64_t ld,
+                        int64_t nt, const double* eps, int64_t lde, int predictive, double* samples, int64_t lds, int maximise,
+                        int top_k, int64_t* top_index, double* top_values, double* top_dvalues, int on_device);
+
 /* Training-set residual statistics with the model state left by the last evaluation (which must have had
  * targets): means[i] = K_nm[i,:] . coeffs over the resident training inputs (Trained.calc_means,
  * lib/fitc_gp.ml:296-297; host, n doubles, may be NULL) and

@@ -737,6 +737,38 @@ struct Make_deriv {
         return a;
       }
     };
+    // Posterior sample paths (gprhip_sample_paths: an extension beyond the reference's implemented surface).  A sampler keeps
+    // the caller's m x ns standard normal draws z: the same sampler evaluates the same ns functions at any inputs.
+    struct Path_sampler_t {
+      const Trained_t* trained;
+      Mat z;  // m x ns
+    };
+    struct Path_best_t {
+      std::vector<int64_t> top_index;  // top_k x ns (-1 where fewer qualify)
+      Vec top_values;                  // top_k x ns
+      Vec top_dvalues;                 // D x top_k x ns: gradient of the path part at each winner
+    };
+    struct Path_sampler {
+      static Path_sampler_t calc(const Trained_t& trained, const Mat& z) { return Path_sampler_t{&trained, z}; }
+      // nt x ns samples; eps (nt x ns standard normal draws) or nullptr for the path part alone
+      static Mat samples(const Path_sampler_t& s, const Inputs_t& in, const Mat* eps = nullptr, bool predictive = false) {
+        Problem& p = problem_for(*s.trained, in, "Path_sampler.samples");
+        Mat out(in.points->cols, s.z.cols);
+        check(gprhip_sample_paths(p.get(), s.z.data(), s.z.rows, s.z.cols, in.points->data(), in.points->rows, in.points->cols,
+                                  eps ? eps->data() : nullptr, eps ? eps->rows : 0, predictive ? 1 : 0, out.data(), out.rows, 1, 0,
+                                  nullptr, nullptr, nullptr, 0));
+        return out;
+      }
+      static Path_best_t best(const Path_sampler_t& s, const Inputs_t& in, int k, bool maximise = true) {
+        Problem& p = problem_for(*s.trained, in, "Path_sampler.best");
+        const size_t kk = (size_t)(k > 0 ? k : 0) * (size_t)s.z.cols;
+        Path_best_t b{std::vector<int64_t>(kk, -1), Vec(kk), Vec(kk * (size_t)in.points->rows)};
+        check(gprhip_sample_paths(p.get(), s.z.data(), s.z.rows, s.z.cols, in.points->data(), in.points->rows, in.points->cols,
+                                  nullptr, 0, 0, nullptr, 0, maximise ? 1 : 0, k, b.top_index.data(), b.top_values.data(),
+                                  b.top_dvalues.data(), 0));
+        return b;
+      }
+    };
     struct Covariances {  // FITC_covariances / FIC_covariances, :565-627
       template <class Owner>
       static Covariances_t calc(const Owner& cvp, double sigma2, const Inputs_t& in) {
