@@ -109,6 +109,22 @@ using GemmArgsF = GemmArgsT<float>;
 void launch_gemm(GemmOp op, const GemmArgs& g, hipStream_t stream);
 void launch_gemm(GemmOp op, const GemmArgsF& g, hipStream_t stream);
 
+// The geometry launch_gemm decides for a launch, as a host function of the arguments (and of the per-process switches
+// and the device's slot count, so call it after gemm_init): the fields it sets in the kernel's arguments, the item count,
+// the grid and which of the seven kernels of a type goes out.  launch_gemm calls it; tools/engine_modes_check.hip prints
+// it and asserts that a case took the path it is named for.
+enum GemmKernel : int { GK_NN = 0, GK_NT, GK_NT_XT, GK_NT_SX, GK_TN, GK_TN_W, GK_TN_WS };
+struct GemmPlan {
+  int kernel = GK_NN;
+  int ipw = 1, pair_split = 0, tail_panels = 0, desc2 = 0, syrk = 0, dslices = 0, sgroup = 16;  // as in GemmArgsT
+  int order = 0;      // the caller's order, or 0 where a short paired launch falls back to single column tiles
+  int work = 0;       // items (tile x k-slice) of one problem of the launch
+  int grid_x = 0, grid_y = 1;
+};
+GemmPlan gemm_plan(GemmOp op, const GemmArgs& g);
+GemmPlan gemm_plan(GemmOp op, const GemmArgsF& g);
+const char* gemm_kernel_name(int kernel, bool f64);
+
 // A weighted upper_only TN launch with A == B (SYRK-shaped) split `kslices` ways (a multiple of 8) gives its diagonal
 // tiles fewer, longer k-slices: their partial products (and the column sums) occupy slice buffers 0 .. this - 1 only.
 int gemm_syrk_diag_slices(int kslices, bool f64, bool col_sums);
