@@ -34,6 +34,11 @@ def _record(what, err, tol, **extra):
         f.write(json.dumps(rec) + "\n")
 
 
+def record(what, err, tol, **extra):
+    """One line {test, what, err, tol, ...} in the GPR_MARGINS_LOG of the run, for figures a test computes itself."""
+    _record(what, err, tol, **extra)
+
+
 def families(kind, d, m, D=0, proj=False, het=False, ms=False):
     """[(family, slice)] of the gradient vector in the reference's Hyper.get_all order."""
     out, pos = [], 0

@@ -179,31 +179,33 @@ def cond_of(a):
     return float(w[-1] / w[0]) if w[0] > 0 else np.inf
 
 
-def factor_case(kind, n, m, d=None):
+def factor_case(kind, n, m, d=None, D=None):
     """Inputs, targets, inducing points, Problem.eval arguments, the oracle's kernel, cond(K_m + jitter I) of a case whose
     length scale is CHOSEN as the largest of 0.8^k at which the oracle's K_m + jitter I has a condition number of at most 1e5
     (asserted here: the search may not run out).
-    kind: "iso"; "fat_het" (Cov_se_fat, heteroskedastic noise); "fat_proj_het" (... and a projection from D = d + 2 input
-    dimensions); "fat_ms" (Cov_se_fat with multiscales).  d defaults to 2 for "iso" and 3 otherwise.
+    kind: "iso"; "fat_het" (Cov_se_fat, heteroskedastic noise); "fat_proj_het" (... and a projection from D input dimensions,
+    d + 2 by default, D >= d); "fat_ms" (Cov_se_fat with multiscales); "fat_proj_ms" (multiscales and a projection, no noise).  d defaults to 2 for "iso" and 3 otherwise.
     The points are synth(900 + m, max(n, 800, m), m, d) with the first n training points kept: up to 800 training points every
     n shares the inducing points (and so the length scale) of its m, and n < m is possible."""
     if d is None:
         d = 2 if kind == "iso" else 3
     X, y, Z = synth(900 + m, max(n, FACTOR_N_TRAIN, m), m, d)
     X, y = np.asfortranarray(X[:, :n]), y[:n].copy()
-    het = None if kind in ("iso", "fat_ms") else np.random.default_rng(m).uniform(-7.0, -4.0, size=m)
+    het = None if kind in ("iso", "fat_ms", "fat_proj_ms") else np.random.default_rng(m).uniform(-7.0, -4.0, size=m)
     tproj = lms = None
-    if kind == "fat_proj_het":
+    if kind in ("fat_proj_het", "fat_proj_ms"):
         # tproj = Q A with Q (D x d) orthonormal and A a perturbed identity; the inputs are Q x plus a part orthogonal to
         # Q that the projection removes, so the projected points are A^T x and the inducing points A^T z
         rng = np.random.default_rng(1000 + m)
-        Q, _ = np.linalg.qr(rng.normal(size=(d + 2, d)))
+        D = d + 2 if D is None else D
+        assert D >= d, (D, d)
+        Q, _ = np.linalg.qr(rng.normal(size=(D, d)))
         A = np.eye(d) + 0.1 * rng.uniform(-1.0, 1.0, size=(d, d))
-        off = rng.normal(size=(d + 2, n))
+        off = rng.normal(size=(D, n))
         X = np.asfortranarray(Q @ X + (off - Q @ (Q.T @ off)))
         tproj = np.asfortranarray(Q @ A)
         Z = np.asfortranarray(A.T @ Z)
-    if kind == "fat_ms":
+    if kind in ("fat_ms", "fat_proj_ms"):
         lms = np.asfortranarray(np.random.default_rng(2000 + m).uniform(-1.0, 0.5, size=(d, m)))
     ell = 1.0
     for _ in range(40):
