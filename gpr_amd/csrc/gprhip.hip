@@ -4049,6 +4049,24 @@ int gprhip_debug_fetch(gprhip_problem* p, const char* name, double* out, int64_t
         for (int64_t r = 0; r < rows; ++r) out[(size_t)c * rows + r] = h[(size_t)r * mp + c];
       return;
     }
+    else if (nm == "uinv" || nm == "rinv") {
+      // U^-1 and R~^-1 as the posterior calls read them (after an evaluation of one or several target vectors, or a loaded
+      // predictor with co-variance coefficients): with "t" every posterior output is a short contraction of operands a test
+      // holds exactly.  A copy only; nothing of the model state changes.
+      need_model(p, "gprhip_debug_fetch");
+      if (!p->have_factors) {
+        set_error("gprhip_debug_fetch: \"" + nm + "\" needs the factors of an evaluation, or of a predictor loaded with "
+                  "co-variance coefficients (chol_km, r_mat)");
+        throw HipFail{ST_STATE};
+      }
+      if (len < (int64_t)p->m * p->m) {
+        set_error("gprhip_debug_fetch: \"" + nm + "\" needs m*m doubles");
+        throw HipFail{ST_BAD_ARG};
+      }
+      GPR_HIP(hipSetDevice(p->device));
+      fetch_upper_fortran(p, nm == "uinv" ? p->uinv : p->rinv, out);
+      return;
+    }
     else {
       set_error("gprhip_debug_fetch: unknown name");
       throw HipFail{ST_BAD_ARG};

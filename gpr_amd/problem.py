@@ -531,8 +531,10 @@ class Problem:
 
     def debug_fetch_matrix(self, name, rows=None):
         """"km": K_m of the last evaluation (m x m, upper triangle valid, zeros below); "knm_rows": the first `rows`
-        rows of K_nm rebuilt with the last evaluation's kernel (rows x m)."""
-        if name in ("km", "w_mat"):
+        rows of K_nm rebuilt with the last evaluation's kernel (rows x m); "uinv", "rinv": U^-1 and R~^-1 as the posterior
+        calls read them (m x m, upper triangle, zeros below; they need the factors of an evaluation or of a predictor loaded
+        with co-variance coefficients)."""
+        if name in ("km", "w_mat", "uinv", "rinv"):
             out = np.empty((self.m, self.m), dtype=np.float64, order="F")
         elif name in ("knm_rows", "x_rows"):
             out = np.empty((int(rows), self.m), dtype=np.float64, order="F")

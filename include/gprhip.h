@@ -502,7 +502,10 @@ int gprhip_condition(gprhip_problem* p, double* cond_km, double* coeff_error_bou
  *               rows x m (column-major, leading dimension rows); fp32-bulk problems return the rounded stored values;
  *   "w_mat" m*m : W of Trained.prepare_hyper (lib/fitc_gp.ml:1196-1203) after a gradient evaluation, Fortran m x m, symmetric;
  *   "x_rows" rows*m : the first rows of X (lib/fitc_gp.ml:1204-1206), Fortran rows x m -- fp64 problems whose training
- *               points fit one row chunk only (the chunk buffers are reused otherwise).
+ *               points fit one row chunk only (the chunk buffers are reused otherwise);
+ *   "uinv", "rinv" m*m : U^-1 and R~^-1 as gprhip_predict, gprhip_covariances and the other posterior calls read them,
+ *               Fortran m x m, upper triangle, zeros below -- after gprhip_eval, gprhip_eval_targets, or a
+ *               gprhip_load_predictor with co-variance coefficients (GPRHIP_ESTATE otherwise).  A copy: the state is untouched.
  * Returns GPRHIP_EBADARG for an unknown name. */
 int gprhip_debug_fetch(gprhip_problem* p, const char* name, double* out, int64_t len);
 

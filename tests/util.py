@@ -184,7 +184,7 @@ def factor_case(kind, n, m, d=None, D=None):
     length scale is CHOSEN as the largest of 0.8^k at which the oracle's K_m + jitter I has a condition number of at most 1e5
     (asserted here: the search may not run out).
     kind: "iso"; "fat_het" (Cov_se_fat, heteroskedastic noise); "fat_proj_het" (... and a projection from D input dimensions,
-    d + 2 by default, D >= d); "fat_ms" (Cov_se_fat with multiscales); "fat_proj_ms" (multiscales and a projection, no noise).  d defaults to 2 for "iso" and 3 otherwise.
+    d + 2 by default, D >= d); "fat_ms" (Cov_se_fat with multiscales); "fat_proj_ms" (multiscales and a projection, no noise); "fat_het_ms" (noise and multiscales); "fat_proj_het_ms" (all three options).  d defaults to 2 for "iso" and 3 otherwise.
     The points are synth(900 + m, max(n, 800, m), m, d) with the first n training points kept: up to 800 training points every
     n shares the inducing points (and so the length scale) of its m, and n < m is possible."""
     if d is None:
@@ -193,7 +193,7 @@ def factor_case(kind, n, m, d=None, D=None):
     X, y = np.asfortranarray(X[:, :n]), y[:n].copy()
     het = None if kind in ("iso", "fat_ms", "fat_proj_ms") else np.random.default_rng(m).uniform(-7.0, -4.0, size=m)
     tproj = lms = None
-    if kind in ("fat_proj_het", "fat_proj_ms"):
+    if kind in ("fat_proj_het", "fat_proj_ms", "fat_proj_het_ms"):
         # tproj = Q A with Q (D x d) orthonormal and A a perturbed identity; the inputs are Q x plus a part orthogonal to
         # Q that the projection removes, so the projected points are A^T x and the inducing points A^T z
         rng = np.random.default_rng(1000 + m)
@@ -205,7 +205,7 @@ def factor_case(kind, n, m, d=None, D=None):
         X = np.asfortranarray(Q @ X + (off - Q @ (Q.T @ off)))
         tproj = np.asfortranarray(Q @ A)
         Z = np.asfortranarray(A.T @ Z)
-    if kind in ("fat_ms", "fat_proj_ms"):
+    if kind in ("fat_ms", "fat_proj_ms", "fat_het_ms", "fat_proj_het_ms"):
         lms = np.asfortranarray(np.random.default_rng(2000 + m).uniform(-1.0, 0.5, size=(d, m)))
     ell = 1.0
     for _ in range(40):
