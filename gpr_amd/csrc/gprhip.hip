@@ -22,8 +22,11 @@
 #include "common.h"
 #include "kernels.h"
 #include "mfma_gemm.h"
+#include "predict_plan.h"
 #include "problem_internal.h"
 #include "sample_paths_host.h"
+
+static_assert(gprhip::PLAN_TILE == gprhip::TILE, "predict_plan.h rounds to the engine's tile");
 
 namespace gprhip {
 const std::string& last_error();
@@ -349,6 +352,7 @@ template <> const double* inv_rfull<double>(const gprhip_problem* p) { return p-
 template <> const float* inv_rfull<float>(const gprhip_problem* p) { return p->rfinv_f; }
 
 void need_trustworthy_coeffs(gprhip_problem* p, const char* who);
+void need_factors(gprhip_problem* p, const char* who);
 
 void tstart(gprhip_problem* p, const char* name) {
   if (!p->timer.on) return;
@@ -1900,67 +1904,100 @@ void ensure_predict_scratch(gprhip_problem* p, int64_t chunk) {
   p->xt_rows = chunk;
 }
 
+// The calls that evaluate the model at test points share three steps ("Calls at test points"): a plan of the
+// chunk and of what must grow (predict_plan.h: nothing is allocated), its allocation, and a walk over the chunks.
+
+// few inducing points: a chunk of test points is one kernel (small.hip / predict_grad.hip) that keeps its n x m tiles in LDS
+bool one_kernel_path(const gprhip_problem* p) {
+  return p->small_path && !p->f32 && p->m <= 64 && p->mp == TILE && p->d <= 16 && !p->has_ms();
+}
+
+ChunkPlan chunk_plan(const gprhip_problem* p, int64_t nt, bool mats) {
+  return predict_plan(p->chunk, nt, mats, p->pred_rows, p->xt_rows);
+}
+
+// carries out a plan: predA / predB and the xt / pt / prow scratch, as far as they must grow
+void chunk_alloc(gprhip_problem* p, const ChunkPlan& c) {
+  if (c.grow_pred) {
+    GPR_HIP(hipStreamSynchronize(p->stream));
+    release_buf(p, p->predA);
+    release_buf(p, p->predB);
+    p->pred_rows = 0;
+    p->predA = p->alloc<char>(c.chunk * p->mp * p->esz);
+    p->predB = p->alloc<char>(c.chunk * p->mp * p->esz);
+    p->pred_rows = c.chunk;
+  }
+  ensure_predict_scratch(p, c.chunk);
+}
+
+// Walks nt test points (x, row stride ld) in chunks: uploads a chunk into p->xt unless the points are on the device (then
+// ld == D), projects it into p->pt where the model has a projection, calls body(lo, rows, rows_p, raw, pts) with the device
+// pointers of the raw and the projected points, and synchronises the stream before the buffers are reused by the next chunk
+// (device outputs are complete then).
+template <typename F>
+void walk_chunks(gprhip_problem* p, int64_t chunk, const double* x, int64_t ld, int64_t nt, int on_device, F&& body) {
+  hipStream_t s = p->stream;
+  const int D = p->D, d = p->d;
+  for (int64_t lo = 0; lo < nt; lo += chunk) {
+    const int rows = (int)std::min<int64_t>(chunk, nt - lo);
+    const int rows_p = (int)round_up(rows, TILE);
+    const double* raw = x + lo * ld;
+    if (!on_device) {
+      GPR_HIP(hipMemcpy2DAsync(p->xt, (size_t)D * sizeof(double), raw, (size_t)ld * sizeof(double), (size_t)D * sizeof(double),
+                               (size_t)rows, hipMemcpyHostToDevice, s));
+      raw = p->xt;
+    }
+    const double* pts = raw;
+    if (p->has_proj()) {
+      launch_project(raw, rows, D, d, p->tproj, p->pt, s);
+      pts = p->pt;
+    }
+    body(lo, rows, rows_p, raw, pts);
+    GPR_HIP(hipStreamSynchronize(s));
+  }
+}
+
+// The model-state refusals of these calls, in one order: no model ("... to <verb>"), multiscales (where the call has no
+// kernel for them), no factors (where variances are involved), a several-target state and untrustworthy fp32 coefficients
+// (where means are involved; `after_targets` says where they come from instead).
+void need_posterior_state(gprhip_problem* p, const char* fn, const char* verb, bool refuse_ms, bool want_var, bool want_mean,
+                          const char* after_targets) {
+  if (!p->have_model || p->stage != 0) {
+    set_error(std::string(fn) + ": no completed evaluation to " + verb);
+    throw HipFail{ST_STATE};
+  }
+  if (refuse_ms && p->has_ms()) {
+    set_error(std::string(fn) + ": multiscales are not supported (the model state has log_multiscales_m05)");
+    throw HipFail{ST_BAD_ARG};
+  }
+  if (want_var) need_factors(p, fn);
+  if (want_mean && p->multi_state) {
+    set_error(std::string(fn) + ": the last evaluation was gprhip_eval_targets (several target vectors): " + after_targets);
+    throw HipFail{ST_STATE};
+  }
+  if (want_mean) need_trustworthy_coeffs(p, fn);
+}
+
 // Means.calc / Variances.calc (lib/fitc_gp.ml:418-425, :498-518) at nt test points, chunk by chunk,
 // with the m x m state of the last evaluation: V_t = K_tm U^-1, Q_t = V_t R~^-1 (= K_tm R^-1).
 template <typename TS>
 void do_predict(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_t nt, int predictive,
                 double* means, double* variances) {
-  if (!p->have_model || p->stage != 0) {
-    set_error("gprhip_predict: no completed evaluation to predict from");
-    throw HipFail{ST_STATE};
-  }
-  if (variances && !p->have_factors) {
-    set_error("gprhip_predict: the loaded predictor has no co-variance coefficients (chol_km, r_mat)");
-    throw HipFail{ST_STATE};
-  }
-  if (means && p->multi_state) {
-    set_error("gprhip_predict: the last evaluation was gprhip_eval_targets (several target vectors): means come from "
-              "gprhip_predict_targets, or from gprhip_predict after the next gprhip_eval");
-    throw HipFail{ST_STATE};
-  }
-  if (means) need_trustworthy_coeffs(p, "gprhip_predict");
+  need_posterior_state(p, "gprhip_predict", "predict from", false, variances, means,
+                       "means come from gprhip_predict_targets, or from gprhip_predict after the next gprhip_eval");
   GPR_HIP(hipSetDevice(p->device));
   hipStream_t s = p->stream;
   const int mp = p->mp;
-  // Test points go through in chunks of their own: the training chunk (at most the training set, padded) when that is
-  // enough, else up to 131072 rows in buffers kept for later calls -- a model trained on 2000 points predicts 100 000
-  // test points in one pass instead of 49 (5.4 -> 0.7 ms), each of which ends in a stream synchronisation.
-  int64_t chunk = p->chunk;
-  const int64_t want = std::min<int64_t>(131072, round_up(nt, TILE));
-  const bool proj = p->has_proj();
-  // few inducing points: a chunk is one kernel (small.hip) that keeps its n x m tiles in LDS -- it needs the row buffers
-  // only, not the two chunk x mp matrices (268 MB at 131072 rows that a cached small model would pin for nothing)
-  const bool small = p->small_path && !p->f32 && p->m <= 64 && mp == TILE && p->d <= 16 && !p->has_ms();
-  if (want > chunk) {
-    const int64_t rows = std::min<int64_t>(131072, std::max(want, 8 * chunk));
-    if (!small && p->pred_rows < want) {
-      GPR_HIP(hipStreamSynchronize(s));
-      release_buf(p, p->predA);
-      release_buf(p, p->predB);
-      p->pred_rows = 0;
-      p->predA = p->alloc<char>(rows * mp * p->esz);
-      p->predB = p->alloc<char>(rows * mp * p->esz);
-      p->pred_rows = rows;
-    }
-    chunk = small ? std::max(p->xt_rows >= want ? p->xt_rows : rows, p->chunk) : p->pred_rows;
-  }
-  ensure_predict_scratch(p, chunk);
+  const bool small = one_kernel_path(p);  // it needs the row buffers only, not the two chunk x mp matrices
+  const ChunkPlan plan = chunk_plan(p, nt, !small);
+  chunk_alloc(p, plan);
+  const int64_t chunk = plan.chunk;
   TS* const bufA = static_cast<TS*>(chunk > p->chunk ? p->predA : p->bufA);
   TS* const bufB = static_cast<TS*>(chunk > p->chunk ? p->predB : p->bufB);
   double* rmean = p->prow;
   double* rk = p->prow + chunk;
   double* rb = p->prow + 2 * chunk;
-  for (int64_t lo = 0; lo < nt; lo += chunk) {
-    const int rows = (int)std::min<int64_t>(chunk, nt - lo);
-    const int rows_p = (int)round_up(rows, TILE);
-    GPR_HIP(hipMemcpy2DAsync(p->xt, (size_t)p->D * sizeof(double), test_inputs + lo * ld,
-                             (size_t)ld * sizeof(double), (size_t)p->D * sizeof(double), (size_t)rows,
-                             hipMemcpyHostToDevice, s));
-    const double* pts = p->xt;
-    if (proj) {
-      launch_project(p->xt, rows, p->D, p->d, p->tproj, p->pt, s);
-      pts = p->pt;
-    }
+  walk_chunks(p, chunk, test_inputs, ld, nt, 0, [&](int64_t lo, int rows, int rows_p, const double*, const double* pts) {
     if (small) {  // few inducing points: the whole chunk in one kernel (small.hip)
       SmallPredictArgs a;
       a.cp = p->cp; a.pts = pts; a.Z = p->Z; a.uinv = p->uinv; a.rinv = p->rinv; a.tvec = p->tvec;
@@ -1969,8 +2006,7 @@ void do_predict(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_
       launch_small_predict(a, s);
       if (means) GPR_HIP(hipMemcpyAsync(means + lo, rmean, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, s));
       if (variances) GPR_HIP(hipMemcpyAsync(variances + lo, rk, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, s));
-      GPR_HIP(hipStreamSynchronize(s));
-      continue;
+      return;
     }
     launch_cov_cross<TS>(p->cp, pts, rows, rows_p, p->Z, p->m, mp, p->d, bufA, s);
     if (means) {
@@ -1991,8 +2027,7 @@ void do_predict(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_
       launch_variance_combine(rk, rb, rows, p->cp.sf2, predictive ? p->h.sigma2 : 0.0, rk, s);
       GPR_HIP(hipMemcpyAsync(variances + lo, rk, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, s));
     }
-    GPR_HIP(hipStreamSynchronize(s));  // xt / row buffers are reused by the next chunk
-  }
+  });
 }
 
 // gprhip_predict_input_grad: M = U^-1 (I - R~^-1 R~^-T) U^-T of the current model state (full symmetric), with the m x m
@@ -2018,13 +2053,13 @@ void ensure_predict_m(gprhip_problem* p) {
   p->pg_m_valid = true;
 }
 
-// The buffers of one call of gprhip_predict_input_grad / gprhip_acquire: the chunk rule of do_predict, M, the chunk buffers and
+// The buffers of one call of gprhip_predict_input_grad / gprhip_acquire: the chunk plan, M, the chunk buffers and
 // the gradient staging, allocated after a look at the device's free memory (a refusal leaves the problem as it was).
 // want_var: K and G of a chunk are needed (matrices in memory unless the one-kernel path serves the shape);
 // host_g: a gradient matrix is staged on the device ([rows][D]) in front of a transfer
 struct PgPlan {
   int64_t chunk;
-  bool small, mats, proj;
+  bool small, mats;
   double *stage_g[2], *stage_p[2];  // gradient staging [rows][D] (host part) and [rows][d] (in front of the projection)
   double *bufA, *bufB;              // K and G of a chunk
   double *rmean, *rvar, *rval;      // three row vectors of xt_rows entries
@@ -2035,24 +2070,13 @@ PgPlan pg_prepare(gprhip_problem* p, const char* fn, int64_t nt, bool want_var, 
   hipStream_t s = p->stream;
   const int mp = p->mp, D = p->D, d = p->d;
   const bool proj = p->has_proj();
-  const bool small = p->small_path && p->m <= 64 && mp == TILE && d <= 16;
+  const bool small = one_kernel_path(p);
   const bool mats = !small && want_var;  // K and G of a chunk are matrices in memory
-  // the chunk rule of do_predict
-  int64_t chunk = p->chunk;
-  const int64_t want = std::min<int64_t>(131072, round_up(nt, TILE));
-  bool grow_pred = false;
-  if (want > chunk) {
-    const int64_t rows = std::min<int64_t>(131072, std::max(want, 8 * chunk));
-    if (mats) {
-      grow_pred = p->pred_rows < want;
-      chunk = grow_pred ? rows : p->pred_rows;
-    } else {
-      chunk = std::max(p->xt_rows >= want ? p->xt_rows : rows, p->chunk);
-    }
-  }
+  const ChunkPlan cplan = chunk_plan(p, nt, mats);
+  const int64_t chunk = cplan.chunk;
+  const bool grow_pred = cplan.grow_pred, grow_xt = cplan.grow_xt;
   // everything this call allocates, after a look at the device's free memory: a refusal leaves the problem as it was
   const bool need_m = mats && with_pg && !p->pg_m;
-  const bool grow_xt = !(p->xt && p->xt_rows >= chunk);
   const bool grow_pg = with_pg && (host_g || proj) && (p->pg_rows < chunk || (host_g && !p->pg_host) || (proj && !p->pg_proj));
   const bool pg_host = host_g || p->pg_host, pg_proj = proj || p->pg_proj;
   const int64_t pg_len = 2 * chunk * ((pg_host ? D : 0) + (pg_proj ? d : 0));
@@ -2072,16 +2096,7 @@ PgPlan pg_prepare(gprhip_problem* p, const char* fn, int64_t nt, bool want_var, 
     }
   }
   if (need_m) p->pg_m = p->alloc<double>((int64_t)mp * mp);
-  if (grow_pred) {
-    GPR_HIP(hipStreamSynchronize(s));
-    release_buf(p, p->predA);
-    release_buf(p, p->predB);
-    p->pred_rows = 0;
-    p->predA = p->alloc<char>(chunk * mp * p->esz);
-    p->predB = p->alloc<char>(chunk * mp * p->esz);
-    p->pred_rows = chunk;
-  }
-  ensure_predict_scratch(p, chunk);
+  chunk_alloc(p, cplan);
   if (grow_pg) {
     GPR_HIP(hipStreamSynchronize(s));
     release_buf(p, p->pg_buf);
@@ -2093,7 +2108,7 @@ PgPlan pg_prepare(gprhip_problem* p, const char* fn, int64_t nt, bool want_var, 
   }
   const int64_t pgr = p->pg_rows;
   PgPlan plan;
-  plan.chunk = chunk; plan.small = small; plan.mats = mats; plan.proj = proj;
+  plan.chunk = chunk; plan.small = small; plan.mats = mats;
   plan.stage_g[0] = p->pg_buf;                                               // [rows][D] (host part)
   plan.stage_g[1] = p->pg_buf ? p->pg_buf + pgr * D : nullptr;
   double* const stage_p0 = p->pg_buf ? p->pg_buf + (p->pg_host ? 2 * pgr * D : 0) : nullptr;
@@ -2107,92 +2122,87 @@ PgPlan pg_prepare(gprhip_problem* p, const char* fn, int64_t nt, bool want_var, 
   return plan;
 }
 
-// Means / variances of do_predict and their gradients with respect to the test inputs (predict_grad.hip), chunk by chunk with
-// do_predict's buffers and chunk rule.  The caller has checked the arguments and the limits.
+// One chunk of the prediction gradient on the device: K and G = K M where the plan keeps them in memory, then the gradient
+// kernel (predict_grad.hip; the one-kernel variant for few inducing points) and the back-projection of its d/dp where the
+// model has a projection.  dst[q]: where the [rows][D] gradients end up (mean, variance; null: not wanted); acq: the criterion
+// epilogue of gprhip_acquire, whose one gradient goes to dst[0].
+void pg_chunk(gprhip_problem* p, const PgPlan& plan, const double* pts, int rows, int rows_p, bool want_var, double add,
+              double* mean_dev, double* var_dev, double* const dst[2], const AcqArgs* acq) {
+  hipStream_t s = p->stream;
+  const int mp = p->mp, D = p->D, d = p->d;
+  const bool proj = p->has_proj();
+  // where the kernel writes: d/dp in front of a projection
+  double* const kout[2] = {dst[0] ? (proj ? plan.stage_p[0] : dst[0]) : nullptr, dst[1] ? (proj ? plan.stage_p[1] : dst[1]) : nullptr};
+  const int64_t kld = proj ? d : D;
+  if (plan.small) {  // few inducing points: the whole chunk in one kernel
+    tstart(p, "pg_grad");
+    SmallPredictGradArgs a;
+    a.cp = p->cp; a.pts = pts; a.Z = p->Z; a.shift = p->zshift; a.uinv = p->uinv; a.rinv = p->rinv; a.tvec = p->tvec;
+    a.rows = rows; a.m = p->m; a.mp = mp; a.d = d; a.want_var = want_var ? 1 : 0; a.add = add;
+    a.means = mean_dev; a.vars = var_dev; a.dmeans = kout[0]; a.dvars = kout[1]; a.ldg = kld;
+    if (acq) launch_small_acquire_grad(a, *acq, s);
+    else launch_small_predict_grad(a, s);
+  } else {
+    if (plan.mats) {
+      tstart(p, "pg_cov");
+      launch_cov_cross<double>(p->cp, pts, rows, rows_p, p->Z, p->m, mp, d, plan.bufA, s);
+      tstop(p);
+      tstart(p, "pg_gemm");
+      GemmArgs g;  // G = K M
+      g.A = plan.bufA; g.lda = mp; g.B = p->pg_m; g.ldb = mp; g.C = plan.bufB; g.ldc = mp;
+      g.M = rows_p; g.N = mp; g.K = mp;
+      launch_gemm(OP_NN, g, s);
+      tstop(p);
+    }
+    tstart(p, "pg_grad");
+    PredictGradArgs a;
+    a.pts = pts; a.Z = p->Z; a.shift = p->zshift; a.tvec = p->tvec; a.G = plan.mats ? plan.bufB : nullptr;
+    a.rows = rows; a.m = p->m; a.mp = mp; a.d = d;
+    a.log_sf2 = p->cp.log_sf2; a.inv_ell2_05 = p->cp.inv_ell2_05; a.sf2 = p->cp.sf2; a.add = add;
+    a.means = mean_dev; a.vars = var_dev; a.dmeans = kout[0]; a.dvars = kout[1]; a.ldg = kld;
+    if (acq) launch_acquire_grad(a, *acq, s);
+    else launch_predict_grad(a, s);
+  }
+  if (proj)
+    for (int q = 0; q < 2; ++q)
+      if (dst[q]) launch_input_grad_project(kout[q], rows, d, D, p->tproj, dst[q], D, s);
+  tstop(p);
+}
+
+// the best k of a call, best first, into its three outputs (top_values / top_dvalues may be null)
+void write_topk(const SpBest& best, int top_k, int D, int64_t* top_index, double* top_values, double* top_dvalues) {
+  for (int j = 0; j < top_k; ++j) {
+    if (j >= (int)best.idx.size()) {
+      top_index[j] = -1;  // fewer than top_k candidates qualify: their values and gradients are left as they are
+      continue;
+    }
+    top_index[j] = best.idx[j];
+    if (top_values) top_values[j] = best.val[j];
+    if (top_dvalues) std::copy(best.grad.begin() + (size_t)j * D, best.grad.begin() + (size_t)(j + 1) * D, top_dvalues + (int64_t)j * D);
+  }
+}
+
+// Means / variances of do_predict and their gradients with respect to the test inputs (predict_grad.hip), chunk by chunk.
+// The caller has checked the arguments and the limits.
 void do_predict_input_grad(gprhip_problem* p, const double* test_inputs, int64_t ld, int64_t nt, int predictive, double* means,
                            double* variances, double* dmeans, double* dvariances, int64_t ldg, int on_device) {
   const bool want_mean = means || dmeans, want_var = variances || dvariances;
-  if (!p->have_model || p->stage != 0) {
-    set_error("gprhip_predict_input_grad: no completed evaluation to predict from");
-    throw HipFail{ST_STATE};
-  }
-  if (p->has_ms()) {
-    set_error("gprhip_predict_input_grad: multiscales are not supported (the model state has log_multiscales_m05)");
-    throw HipFail{ST_BAD_ARG};
-  }
-  if (want_var && !p->have_factors) {
-    set_error("gprhip_predict_input_grad: the loaded predictor has no co-variance coefficients (chol_km, r_mat)");
-    throw HipFail{ST_STATE};
-  }
-  if (want_mean && p->multi_state) {
-    set_error("gprhip_predict_input_grad: the last evaluation was gprhip_eval_targets (several target vectors): means and "
-              "their gradients are available after the next gprhip_eval");
-    throw HipFail{ST_STATE};
-  }
-  if (want_mean) need_trustworthy_coeffs(p, "gprhip_predict_input_grad");
+  need_posterior_state(p, "gprhip_predict_input_grad", "predict from", true, want_var, want_mean,
+                       "means and their gradients are available after the next gprhip_eval");
   GPR_HIP(hipSetDevice(p->device));
   hipStream_t s = p->stream;
-  const int mp = p->mp, D = p->D, d = p->d;
+  const int D = p->D;
   const PgPlan plan = pg_prepare(p, "gprhip_predict_input_grad", nt, want_var, !on_device && (dmeans || dvariances));
-  const bool proj = plan.proj, small = plan.small, mats = plan.mats;
-  const int64_t chunk = plan.chunk;
-  double* const stage_g[2] = {plan.stage_g[0], plan.stage_g[1]};
-  double* const stage_p[2] = {plan.stage_p[0], plan.stage_p[1]};
-  double *const bufA = plan.bufA, *const bufB = plan.bufB, *const rmean = plan.rmean, *const rvar = plan.rvar;
-  if (mats) ensure_predict_m(p);
+  double *const rmean = plan.rmean, *const rvar = plan.rvar;
+  if (plan.mats) ensure_predict_m(p);
   const double add = predictive ? p->h.sigma2 : 0.0;
-  for (int64_t lo = 0; lo < nt; lo += chunk) {
-    const int rows = (int)std::min<int64_t>(chunk, nt - lo);
-    const int rows_p = (int)round_up(rows, TILE);
-    const double* xin = test_inputs + lo * D;
-    if (!on_device) {
-      GPR_HIP(hipMemcpy2DAsync(p->xt, (size_t)D * sizeof(double), test_inputs + lo * ld, (size_t)ld * sizeof(double),
-                               (size_t)D * sizeof(double), (size_t)rows, hipMemcpyHostToDevice, s));
-      xin = p->xt;
-    }
-    const double* pts = xin;
-    if (proj) {
-      launch_project(xin, rows, D, d, p->tproj, p->pt, s);
-      pts = p->pt;
-    }
-    // where the outputs of this chunk end up on the device, and where the kernel writes (d/dp in front of a projection)
+  walk_chunks(p, plan.chunk, test_inputs, ld, nt, on_device, [&](int64_t lo, int rows, int rows_p, const double*, const double* pts) {
+    // where the outputs of this chunk end up on the device
     double* const mean_dev = means ? (on_device ? means + lo : rmean) : nullptr;
     double* const var_dev = variances ? (on_device ? variances + lo : rvar) : nullptr;
-    double* const dst[2] = {dmeans ? (on_device ? dmeans + lo * D : stage_g[0]) : nullptr,
-                            dvariances ? (on_device ? dvariances + lo * D : stage_g[1]) : nullptr};
-    double* const kout[2] = {dst[0] ? (proj ? stage_p[0] : dst[0]) : nullptr, dst[1] ? (proj ? stage_p[1] : dst[1]) : nullptr};
-    const int64_t kld = proj ? d : D;
-    if (small) {  // few inducing points: the whole chunk in one kernel
-      tstart(p, "pg_grad");
-      SmallPredictGradArgs a;
-      a.cp = p->cp; a.pts = pts; a.Z = p->Z; a.shift = p->zshift; a.uinv = p->uinv; a.rinv = p->rinv; a.tvec = p->tvec;
-      a.rows = rows; a.m = p->m; a.mp = mp; a.d = d; a.want_var = want_var ? 1 : 0; a.add = add;
-      a.means = mean_dev; a.vars = var_dev; a.dmeans = kout[0]; a.dvars = kout[1]; a.ldg = kld;
-      launch_small_predict_grad(a, s);
-    } else {
-      if (mats) {
-        tstart(p, "pg_cov");
-        launch_cov_cross<double>(p->cp, pts, rows, rows_p, p->Z, p->m, mp, d, bufA, s);
-        tstop(p);
-        tstart(p, "pg_gemm");
-        GemmArgs g;  // G = K M
-        g.A = bufA; g.lda = mp; g.B = p->pg_m; g.ldb = mp; g.C = bufB; g.ldc = mp;
-        g.M = rows_p; g.N = mp; g.K = mp;
-        launch_gemm(OP_NN, g, s);
-        tstop(p);
-      }
-      tstart(p, "pg_grad");
-      PredictGradArgs a;
-      a.pts = pts; a.Z = p->Z; a.shift = p->zshift; a.tvec = p->tvec; a.G = mats ? bufB : nullptr;
-      a.rows = rows; a.m = p->m; a.mp = mp; a.d = d;
-      a.log_sf2 = p->cp.log_sf2; a.inv_ell2_05 = p->cp.inv_ell2_05; a.sf2 = p->cp.sf2; a.add = add;
-      a.means = mean_dev; a.vars = var_dev; a.dmeans = kout[0]; a.dvars = kout[1]; a.ldg = kld;
-      launch_predict_grad(a, s);
-    }
-    if (proj)
-      for (int q = 0; q < 2; ++q)
-        if (dst[q]) launch_input_grad_project(kout[q], rows, d, D, p->tproj, dst[q], D, s);
-    tstop(p);
+    double* const dst[2] = {dmeans ? (on_device ? dmeans + lo * D : plan.stage_g[0]) : nullptr,
+                            dvariances ? (on_device ? dvariances + lo * D : plan.stage_g[1]) : nullptr};
+    pg_chunk(p, plan, pts, rows, rows_p, want_var, add, mean_dev, var_dev, dst, nullptr);
     if (!on_device) {
       if (means) GPR_HIP(hipMemcpyAsync(means + lo, rmean, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, s));
       if (variances) GPR_HIP(hipMemcpyAsync(variances + lo, rvar, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -2202,8 +2212,7 @@ void do_predict_input_grad(gprhip_problem* p, const double* test_inputs, int64_t
           GPR_HIP(hipMemcpy2DAsync(host[q] + lo * ldg, (size_t)ldg * sizeof(double), dst[q], (size_t)D * sizeof(double),
                                    (size_t)D * sizeof(double), (size_t)rows, hipMemcpyDeviceToHost, s));
     }
-    GPR_HIP(hipStreamSynchronize(s));  // the chunk buffers are reused by the next chunk; device outputs are complete
-  }
+  });
   if (p->timer.on) tcollect(p);
 }
 
@@ -2215,31 +2224,14 @@ void do_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const double* 
                 double* values, double* dvalues, int64_t ldg, double* means, double* variances, int top_k, int64_t* top_index,
                 double* top_values, double* top_dvalues, int on_device) {
   const bool want_var = !(acq->kind == GPRHIP_ACQ_BOUND && acq->kappa == 0.0) || variances;
-  if (!p->have_model || p->stage != 0) {
-    set_error("gprhip_acquire: no completed evaluation to predict from");
-    throw HipFail{ST_STATE};
-  }
-  if (p->has_ms()) {
-    set_error("gprhip_acquire: multiscales are not supported (the model state has log_multiscales_m05)");
-    throw HipFail{ST_BAD_ARG};
-  }
-  if (want_var && !p->have_factors) {
-    set_error("gprhip_acquire: the loaded predictor has no co-variance coefficients (chol_km, r_mat)");
-    throw HipFail{ST_STATE};
-  }
-  if (p->multi_state) {
-    set_error("gprhip_acquire: the last evaluation was gprhip_eval_targets (several target vectors): means and "
-              "their gradients are available after the next gprhip_eval");
-    throw HipFail{ST_STATE};
-  }
-  need_trustworthy_coeffs(p, "gprhip_acquire");
+  need_posterior_state(p, "gprhip_acquire", "predict from", true, want_var, true,
+                       "means and their gradients are available after the next gprhip_eval");
   GPR_HIP(hipSetDevice(p->device));
   hipStream_t s = p->stream;
-  const int mp = p->mp, D = p->D, d = p->d;
+  const int D = p->D;
   const bool want_grad = dvalues || (top_k > 0 && top_dvalues);
   const bool stage_grad = want_grad && !(on_device && dvalues);  // the gradient of a chunk stays in the library's staging
   const PgPlan plan = pg_prepare(p, "gprhip_acquire", nt, want_var, stage_grad);
-  const int64_t chunk = plan.chunk;
   if (top_k > 0 && !p->acq_scratch) {
     p->acq_scratch = p->alloc<char>(acq_select_scratch_bytes());
     p->acq_out = p->alloc<double>((int64_t)ACQ_MAX_TOP_K * (D + 2));
@@ -2251,59 +2243,15 @@ void do_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const double* 
   q.kind = acq->kind; q.s = acq->maximise ? 1.0 : -1.0; q.best = acq->best; q.xi = acq->xi; q.kappa = acq->kappa;
   q.var_floor = acq->var_floor;
   const double add = acq->predictive ? p->h.sigma2 : 0.0;
-  // the best so far, over the chunks done
-  std::vector<int64_t> best_idx;
-  std::vector<double> best_val, best_grad;
-  for (int64_t lo = 0; lo < nt; lo += chunk) {
-    const int rows = (int)std::min<int64_t>(chunk, nt - lo);
-    const int rows_p = (int)round_up(rows, TILE);
-    const double* xin = test_inputs + lo * D;
-    if (!on_device) {
-      GPR_HIP(hipMemcpy2DAsync(p->xt, (size_t)D * sizeof(double), test_inputs + lo * ld, (size_t)ld * sizeof(double),
-                               (size_t)D * sizeof(double), (size_t)rows, hipMemcpyHostToDevice, s));
-      xin = p->xt;
-    }
-    const double* pts = xin;
-    if (plan.proj) {
-      launch_project(xin, rows, D, d, p->tproj, p->pt, s);
-      pts = p->pt;
-    }
+  SpBest best;  // the best so far, over the chunks done
+  walk_chunks(p, plan.chunk, test_inputs, ld, nt, on_device, [&](int64_t lo, int rows, int rows_p, const double*, const double* pts) {
     double* const mean_dev = means ? (on_device ? means + lo : plan.rmean) : nullptr;
     double* const var_dev = variances ? (on_device ? variances + lo : plan.rvar) : nullptr;
     double* const val_dev = (values && on_device) ? values + lo : ((values || top_k > 0) ? plan.rval : nullptr);
     double* const dst = want_grad ? (stage_grad ? plan.stage_g[0] : dvalues + lo * D) : nullptr;
-    double* const kout = dst ? (plan.proj ? plan.stage_p[0] : dst) : nullptr;  // d/dp in front of a projection
-    const int64_t kld = plan.proj ? d : D;
+    double* const dsts[2] = {dst, nullptr};
     q.values = val_dev;
-    if (plan.small) {  // few inducing points: the whole chunk in one kernel
-      tstart(p, "pg_grad");
-      SmallPredictGradArgs a;
-      a.cp = p->cp; a.pts = pts; a.Z = p->Z; a.shift = p->zshift; a.uinv = p->uinv; a.rinv = p->rinv; a.tvec = p->tvec;
-      a.rows = rows; a.m = p->m; a.mp = mp; a.d = d; a.want_var = want_var ? 1 : 0; a.add = add;
-      a.means = mean_dev; a.vars = var_dev; a.dmeans = kout; a.dvars = nullptr; a.ldg = kld;
-      launch_small_acquire_grad(a, q, s);
-    } else {
-      if (plan.mats) {
-        tstart(p, "pg_cov");
-        launch_cov_cross<double>(p->cp, pts, rows, rows_p, p->Z, p->m, mp, d, plan.bufA, s);
-        tstop(p);
-        tstart(p, "pg_gemm");
-        GemmArgs g;  // G = K M
-        g.A = plan.bufA; g.lda = mp; g.B = p->pg_m; g.ldb = mp; g.C = plan.bufB; g.ldc = mp;
-        g.M = rows_p; g.N = mp; g.K = mp;
-        launch_gemm(OP_NN, g, s);
-        tstop(p);
-      }
-      tstart(p, "pg_grad");
-      PredictGradArgs a;
-      a.pts = pts; a.Z = p->Z; a.shift = p->zshift; a.tvec = p->tvec; a.G = plan.mats ? plan.bufB : nullptr;
-      a.rows = rows; a.m = p->m; a.mp = mp; a.d = d;
-      a.log_sf2 = p->cp.log_sf2; a.inv_ell2_05 = p->cp.inv_ell2_05; a.sf2 = p->cp.sf2; a.add = add;
-      a.means = mean_dev; a.vars = var_dev; a.dmeans = kout; a.dvars = nullptr; a.ldg = kld;
-      launch_acquire_grad(a, q, s);
-    }
-    if (plan.proj && dst) launch_input_grad_project(kout, rows, d, D, p->tproj, dst, D, s);
-    tstop(p);
+    pg_chunk(p, plan, pts, rows, rows_p, want_var, add, mean_dev, var_dev, dsts, &q);
     if (!on_device) {
       if (values) GPR_HIP(hipMemcpyAsync(values + lo, val_dev, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, s));
       if (means) GPR_HIP(hipMemcpyAsync(means + lo, plan.rmean, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -2327,49 +2275,17 @@ void do_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const double* 
       const int64_t blk = (int64_t)top_k * (gather_g ? D + 2 : 2);
       GPR_HIP(hipMemcpyAsync(p->acq_host, p->acq_out, (size_t)blk * sizeof(double), hipMemcpyDeviceToHost, s));
       GPR_HIP(hipStreamSynchronize(s));
-      // merge: both lists are sorted; an earlier entry (a lower index) stays in front of an equal later one
+      // (the device has sorted by the value itself: sign +1; an earlier entry stays in front of an equal later one)
       const double* const hi = p->acq_host;
-      const double* const hv = hi + top_k;
-      const double* const hg = hv + top_k;
-      std::vector<int64_t> m_idx;
-      std::vector<double> m_val, m_grad;
-      size_t ia = 0;
-      int ib = 0;
-      while ((int)m_idx.size() < top_k) {
-        const bool has_a = ia < best_idx.size(), has_b = ib < top_k && hi[ib] >= 0.0;
-        if (!has_a && !has_b) break;
-        if (has_a && (!has_b || !(hv[ib] > best_val[ia]))) {
-          m_idx.push_back(best_idx[ia]);
-          m_val.push_back(best_val[ia]);
-          if (gather_g) m_grad.insert(m_grad.end(), best_grad.begin() + ia * D, best_grad.begin() + (ia + 1) * D);
-          ++ia;
-        } else {
-          m_idx.push_back(lo + po + (int64_t)hi[ib]);
-          m_val.push_back(hv[ib]);
-          if (gather_g) m_grad.insert(m_grad.end(), hg + (int64_t)ib * D, hg + (int64_t)(ib + 1) * D);
-          ++ib;
-        }
-      }
-      best_idx.swap(m_idx);
-      best_val.swap(m_val);
-      best_grad.swap(m_grad);
+      sp_merge_topk(best, top_k, 1.0, hi, hi + top_k, gather_g ? hi + 2 * top_k : nullptr, D, lo + po);
     }
-    GPR_HIP(hipStreamSynchronize(s));  // the chunk buffers are reused by the next chunk; device outputs are complete
-  }
-  for (int j = 0; j < top_k; ++j) {
-    if (j >= (int)best_idx.size()) {
-      top_index[j] = -1;  // fewer than top_k candidates qualify: their values and gradients are left as they are
-      continue;
-    }
-    top_index[j] = best_idx[j];
-    if (top_values) top_values[j] = best_val[j];
-    if (top_dvalues) std::copy(best_grad.begin() + (size_t)j * D, best_grad.begin() + (size_t)(j + 1) * D, top_dvalues + (int64_t)j * D);
-  }
+  });
+  write_topk(best, top_k, D, top_index, top_values, top_dvalues);
   if (p->timer.on) tcollect(p);
 }
 
-// gprhip_sample_paths: ns draws of the posterior as functions, evaluated at nt test points chunk by chunk with do_predict's
-// chunk rule (sample_paths.hip).  The weights A = t 1^T + U^-1 (R~^-1 Z) are formed once per call; per chunk one kernel gives
+// gprhip_sample_paths: ns draws of the posterior as functions, evaluated at nt test points chunk by chunk
+// (sample_paths.hip). The weights A = t 1^T + U^-1 (R~^-1 Z) are formed once per call; per chunk one kernel gives
 // F = K A (draw-major; K never reaches memory), with eps the residual standard deviation sqrt(max(0, sf2 - |K_r U^-1|^2 (+
 // sigma2))) eps is added in place, the best top_k of every draw are selected on the device (acquire.hip, one launch pair for
 // all draws), the path gradient is evaluated at them, and the chunks' lists are merged here (sample_paths_host.h).
@@ -2377,45 +2293,27 @@ void do_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const double* 
 void do_sample_paths(gprhip_problem* p, const double* z, int64_t ldz, int ns, const double* test_inputs, int64_t ld, int64_t nt,
                      const double* eps, int64_t lde, int predictive, double* samples, int64_t lds, int maximise, int top_k,
                      int64_t* top_index, double* top_values, double* top_dvalues, int on_device) {
-  if (!p->have_model || p->stage != 0) {
-    set_error("gprhip_sample_paths: no completed evaluation to draw from");
-    throw HipFail{ST_STATE};
-  }
-  if (p->has_ms()) {
-    set_error("gprhip_sample_paths: multiscales are not supported (the model state has log_multiscales_m05)");
-    throw HipFail{ST_BAD_ARG};
-  }
-  if (!p->have_factors) {
-    set_error("gprhip_sample_paths: the loaded predictor has no co-variance coefficients (chol_km, r_mat)");
-    throw HipFail{ST_STATE};
-  }
-  if (p->multi_state) {
-    set_error("gprhip_sample_paths: the last evaluation was gprhip_eval_targets (several target vectors): draws are "
-              "available after the next gprhip_eval");
-    throw HipFail{ST_STATE};
-  }
-  need_trustworthy_coeffs(p, "gprhip_sample_paths");
+  need_posterior_state(p, "gprhip_sample_paths", "draw from", true, true, true, "draws are available after the next gprhip_eval");
   GPR_HIP(hipSetDevice(p->device));
   hipStream_t s = p->stream;
   const int mp = p->mp, m = p->m, D = p->D, d = p->d;
   const bool resid = eps != nullptr;
   const bool stage_f = !(on_device && samples), stage_e = resid && !on_device;
-  // this call's own buffers, as far as they must grow: counted before anything is allocated (an upper bound on the rows of
-  // a chunk is enough for that)
-  const int64_t rows_cap = std::min<int64_t>(round_up(nt, TILE), std::max<int64_t>({131072, p->chunk, p->xt_rows, p->pred_rows}));
+  // this call's own buffers, as far as they must grow: counted from the plan's chunk before anything is allocated
+  const int64_t rows_need =  // rows of a chunk of this call
+      std::min<int64_t>(chunk_plan(p, nt, !one_kernel_path(p) && resid).chunk, round_up(nt, TILE));
   const int64_t piece_rows = (int64_t)ACQ_SELECT_MAX_SLABS * 2048;
   const int64_t out_stride = (int64_t)top_k * (D + 2);
+  const int64_t scratch_need = top_k > 0 ? acq_select_many_scratch_bytes(std::min(rows_need, piece_rows), top_k, ns) : 0;
   int64_t extra = 0;
   if (!p->sp_coef) extra += 2 * (int64_t)mp * SP_MAX_DRAWS * 8;
-  if (stage_f && p->sp_f_rows < ns * rows_cap) extra += ns * rows_cap * 8;
-  if (stage_e && p->sp_eps_rows < ns * rows_cap) extra += ns * rows_cap * 8;
+  if (stage_f && p->sp_f_rows < ns * rows_need) extra += ns * rows_need * 8;
+  if (stage_e && p->sp_eps_rows < ns * rows_need) extra += ns * rows_need * 8;
   if (top_k > 0) {
-    extra += std::max<int64_t>(0, acq_select_many_scratch_bytes(std::min(rows_cap, piece_rows), top_k, ns) - p->sp_scratch_bytes);
+    extra += std::max<int64_t>(0, scratch_need - p->sp_scratch_bytes);
     if (!p->sp_out) extra += (int64_t)SP_MAX_DRAWS * ACQ_MAX_TOP_K * (D + 2) * 8;
   }
   const PgPlan plan = pg_prepare(p, "gprhip_sample_paths", nt, resid, false, false, extra);
-  const int64_t chunk = plan.chunk;
-  const int64_t rows_need = std::min<int64_t>(chunk, round_up(nt, TILE));  // rows of a chunk of this call
   // (the pinned buffer first: a failure leaves both pointers null.  The weight kernel reads it by its host address, as
   //  ship_kernel writes res_host: mapped, portable pinned memory has one address on host and device here)
   if (!p->sp_zhost)
@@ -2437,13 +2335,12 @@ void do_sample_paths(gprhip_problem* p, const double* z, int64_t ldz, int ns, co
     p->sp_eps_rows = ns * rows_need;
   }
   if (top_k > 0) {
-    const int64_t need = acq_select_many_scratch_bytes(std::min(rows_need, piece_rows), top_k, ns);
-    if (p->sp_scratch_bytes < need) {
+    if (p->sp_scratch_bytes < scratch_need) {
       GPR_HIP(hipStreamSynchronize(s));
       release_buf(p, p->sp_scratch);
       p->sp_scratch_bytes = 0;
-      p->sp_scratch = p->alloc<char>(need);
-      p->sp_scratch_bytes = need;
+      p->sp_scratch = p->alloc<char>(scratch_need);
+      p->sp_scratch_bytes = scratch_need;
     }
     if (!p->sp_out) {
       const int64_t len = (int64_t)SP_MAX_DRAWS * ACQ_MAX_TOP_K * (D + 2);
@@ -2463,20 +2360,7 @@ void do_sample_paths(gprhip_problem* p, const double* z, int64_t ldz, int ns, co
   const double sign = maximise ? 1.0 : -1.0;
   const bool want_g = top_k > 0 && top_dvalues;
   std::vector<SpBest> best(top_k > 0 ? ns : 0);
-  for (int64_t lo = 0; lo < nt; lo += chunk) {
-    const int rows = (int)std::min<int64_t>(chunk, nt - lo);
-    const int rows_p = (int)round_up(rows, TILE);
-    const double* xin = test_inputs + lo * D;
-    if (!on_device) {
-      GPR_HIP(hipMemcpy2DAsync(p->xt, (size_t)D * sizeof(double), test_inputs + lo * ld, (size_t)ld * sizeof(double),
-                               (size_t)D * sizeof(double), (size_t)rows, hipMemcpyHostToDevice, s));
-      xin = p->xt;
-    }
-    const double* pts = xin;
-    if (plan.proj) {
-      launch_project(xin, rows, D, d, p->tproj, p->pt, s);
-      pts = p->pt;
-    }
+  walk_chunks(p, plan.chunk, test_inputs, ld, nt, on_device, [&](int64_t lo, int rows, int rows_p, const double*, const double* pts) {
     double* const Fd = stage_f ? p->sp_f : samples + lo;
     const int64_t ldf = stage_f ? rows_need : lds;
     tstart(p, "sp_path");
@@ -2524,7 +2408,7 @@ void do_sample_paths(gprhip_problem* p, const double* z, int64_t ldz, int ns, co
       launch_acq_select_many(sel, s);
       if (want_g) {
         PathGradAtArgs g;
-        g.pts = pts + po * d; g.Z = p->Z; g.shift = p->zshift; g.W = wA; g.tproj = plan.proj ? p->tproj : nullptr;
+        g.pts = pts + po * d; g.Z = p->Z; g.shift = p->zshift; g.W = wA; g.tproj = p->has_proj() ? p->tproj : nullptr;
         g.rows = pr; g.m = m; g.d = d; g.D = D; g.k = top_k; g.ns = ns;
         g.log_sf2 = p->cp.log_sf2; g.inv_ell2_05 = p->cp.inv_ell2_05; g.out = p->sp_out; g.out_stride = out_stride;
         launch_path_grad_at(g, s);
@@ -2537,19 +2421,11 @@ void do_sample_paths(gprhip_problem* p, const double* z, int64_t ldz, int ns, co
         sp_merge_topk(best[j], top_k, sign, blk, blk + top_k, want_g ? blk + 2 * top_k : nullptr, D, lo + po);
       }
     }
-    GPR_HIP(hipStreamSynchronize(s));  // the chunk buffers are reused by the next chunk; device outputs are complete
+  });
+  for (int j = 0; j < ns && top_k > 0; ++j) {
+    const int64_t e = (int64_t)j * top_k;
+    write_topk(best[j], top_k, D, top_index + e, top_values ? top_values + e : nullptr, top_dvalues ? top_dvalues + e * D : nullptr);
   }
-  for (int j = 0; j < ns && top_k > 0; ++j)
-    for (int i = 0; i < top_k; ++i) {
-      const int64_t e = (int64_t)j * top_k + i;
-      if (i >= (int)best[j].idx.size()) {
-        top_index[e] = -1;  // fewer than top_k points qualify: their values and gradients are left as they are
-        continue;
-      }
-      top_index[e] = best[j].idx[i];
-      if (top_values) top_values[e] = best[j].val[i];
-      if (top_dvalues) std::copy(best[j].grad.begin() + (size_t)i * D, best[j].grad.begin() + (size_t)(i + 1) * D, top_dvalues + e * D);
-    }
   if (p->timer.on) tcollect(p);
 }
 
@@ -3037,22 +2913,12 @@ void do_predict_targets(gprhip_problem* p, const double* test_inputs, int64_t ld
   const int64_t chunk = p->chunk, npad = p->npad();
   ensure_predict_scratch(p, chunk);
   double* const K = static_cast<double*>(p->bufA);
-  for (int64_t lo = 0; lo < nt; lo += chunk) {
-    const int rows = (int)std::min<int64_t>(chunk, nt - lo);
-    const int rows_p = (int)round_up(rows, TILE);
-    GPR_HIP(hipMemcpy2DAsync(p->xt, (size_t)p->D * sizeof(double), test_inputs + lo * ld, (size_t)ld * sizeof(double),
-                             (size_t)p->D * sizeof(double), (size_t)rows, hipMemcpyHostToDevice, s));
-    const double* pts = p->xt;
-    if (p->has_proj()) {
-      launch_project(p->xt, rows, p->D, p->d, p->tproj, p->pt, s);
-      pts = p->pt;
-    }
+  walk_chunks(p, chunk, test_inputs, ld, nt, 0, [&](int64_t lo, int rows, int rows_p, const double*, const double* pts) {
     launch_cov_cross<double>(p->cp, pts, rows, rows_p, p->Z, p->m, mp, p->d, K, s);
     launch_targets_rows(K, mp, rows, mp, 0, p->tg_T(), k, p->tg_w, 1, npad, s);  // (W_mat is scratch between evaluations)
     GPR_HIP(hipMemcpy2DAsync(means + lo, (size_t)nt * sizeof(double), p->tg_w, (size_t)npad * sizeof(double),
                              (size_t)rows * sizeof(double), (size_t)k, hipMemcpyDeviceToHost, s));
-    GPR_HIP(hipStreamSynchronize(s));
-  }
+  });
   p->x_last = nullptr;  // (the chunk buffer that may have held X has been overwritten)
 }
 
