@@ -3933,6 +3933,30 @@ int gprhip_debug_fetch(gprhip_problem* p, const char* name, double* out, int64_t
       fetch_upper_fortran(p, nm == "uinv" ? p->uinv : p->rinv, out);
       return;
     }
+    else if (nm == "pg_m") {
+      // M = U^-1 (I - R~^-1 R~^-T) U^-T as pg_chunk's product G = K M reads it (ensure_predict_m), full.  With "t", "uinv" and
+      // "rinv" it makes every output of gprhip_predict_input_grad a short contraction of operands a test holds exactly.
+      // A copy only; nothing of the model state changes.
+      need_model(p, "gprhip_debug_fetch");
+      if (!p->pg_m || !p->pg_m_valid) {
+        set_error("gprhip_debug_fetch: \"pg_m\" needs M of the current model state: it is formed by the first "
+                  "gprhip_predict_input_grad or gprhip_acquire call that asks for a variance part with K and G in memory");
+        throw HipFail{ST_STATE};
+      }
+      const int64_t m = p->m, mp = p->mp;
+      if (len < m * m) {
+        set_error("gprhip_debug_fetch: \"pg_m\" needs m*m doubles");
+        throw HipFail{ST_BAD_ARG};
+      }
+      const int64_t w = len >= mp * mp ? mp : m;  // mp*mp doubles: the padded matrix as it is stored
+      GPR_HIP(hipSetDevice(p->device));
+      std::vector<double> h((size_t)mp * mp);
+      GPR_HIP(hipMemcpyAsync(h.data(), p->pg_m, h.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+      GPR_HIP(hipStreamSynchronize(p->stream));
+      for (int64_t c = 0; c < w; ++c)
+        for (int64_t r = 0; r < w; ++r) out[(size_t)(c * w + r)] = h[(size_t)(r * mp + c)];
+      return;
+    }
     else {
       set_error("gprhip_debug_fetch: unknown name");
       throw HipFail{ST_BAD_ARG};

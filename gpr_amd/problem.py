@@ -533,8 +533,13 @@ class Problem:
         """"km": K_m of the last evaluation (m x m, upper triangle valid, zeros below); "knm_rows": the first `rows`
         rows of K_nm rebuilt with the last evaluation's kernel (rows x m); "uinv", "rinv": U^-1 and R~^-1 as the posterior
         calls read them (m x m, upper triangle, zeros below; they need the factors of an evaluation or of a predictor loaded
-        with co-variance coefficients)."""
-        if name in ("km", "w_mat", "uinv", "rinv"):
+        with co-variance coefficients); "pg_m": M = U^-1 (I - R~^-1 R~^-T) U^-T as the product G = K M of predict_input_grad
+        and acquire reads it (m x m, full; available once such a call has formed it -- stage "pg_m" --, until the next
+        evaluation or load_predictor; `rows` = m rounded up to a multiple of 128 returns the padded matrix as it is stored)."""
+        if name == "pg_m":
+            w = self.m if rows is None else int(rows)
+            out = np.empty((w, w), dtype=np.float64, order="F")
+        elif name in ("km", "w_mat", "uinv", "rinv"):
             out = np.empty((self.m, self.m), dtype=np.float64, order="F")
         elif name in ("knm_rows", "x_rows"):
             out = np.empty((int(rows), self.m), dtype=np.float64, order="F")

@@ -506,6 +506,11 @@ int gprhip_condition(gprhip_problem* p, double* cond_km, double* coeff_error_bou
  *   "uinv", "rinv" m*m : U^-1 and R~^-1 as gprhip_predict, gprhip_covariances and the other posterior calls read them,
  *               Fortran m x m, upper triangle, zeros below -- after gprhip_eval, gprhip_eval_targets, or a
  *               gprhip_load_predictor with co-variance coefficients (GPRHIP_ESTATE otherwise).  A copy: the state is untouched.
+ *   "pg_m" m*m : M = U^-1 (I - R~^-1 R~^-T) U^-T as the product G = K M of gprhip_predict_input_grad and gprhip_acquire reads
+ *               it, Fortran m x m, full -- once a call of either has asked for a variance part with more than 64 inducing
+ *               points or more than 16 point dimensions (stage "pg_m"), until the next evaluation or gprhip_load_predictor
+ *               (GPRHIP_ESTATE otherwise).  With len >= mp*mp, mp = m rounded up to a multiple of 128, the padded
+ *               mp x mp matrix as it is stored.  A copy: the state is untouched.
  * Returns GPRHIP_EBADARG for an unknown name. */
 int gprhip_debug_fetch(gprhip_problem* p, const char* name, double* out, int64_t len);
 
