@@ -54,6 +54,11 @@ external predict_input_grad : problem -> mat -> mat option -> mat option -> unit
 (* an acquisition criterion over the points and its gradient with respect to them (gprhip_acquire); the vector is
    [| kind; maximise; predictive; best; xi; kappa; var_floor |], kind 0 EI, 1 log EI, 2 PI, 3 bound *)
 external acquire : problem -> vec -> mat -> vec option -> mat option -> unit = "gprhip_ml_acquire"
+(* refines the starts (D x ns) of an acquisition criterion inside a box by projected gradient ascent
+   (gprhip_acquire_refine): params as acquire -> options [| max_evals; step0; c1; shrink; grow; xtol |] -> box (D x 2: lower,
+   upper) -> starts -> x_out (D x ns) -> values (ns) *)
+external acquire_refine : problem -> vec -> vec -> mat -> mat -> mat -> vec -> unit
+  = "gprhip_ml_acquire_refine_bc" "gprhip_ml_acquire_refine"
 (* posterior sample paths (gprhip_sample_paths): z (m x ns normal draws) -> points -> eps (nt x ns, or None: the path part
    alone) -> samples (nt x ns) *)
 external sample_paths : problem -> mat -> mat -> mat option -> mat -> unit = "gprhip_ml_sample_paths"

@@ -191,6 +191,56 @@ CAMLprim value gprhip_ml_acquire(value prob, value params, value points, value v
   CAMLreturn(Val_unit);
 }
 
+/* external acquire_refine : problem -> vec -> vec -> mat -> mat -> mat -> vec -> unit
+ *   refines the starts (D x ns) of an acquisition criterion inside a box (gprhip_acquire_refine): params as acquire,
+ *   options [| max_evals; step0; c1; shrink; grow; xtol |], box D x 2 (lower, upper), x_out D x ns, values ns */
+CAMLprim value gprhip_ml_acquire_refine(value prob, value params, value options, value box, value starts, value x_out,
+                                        value values) {
+  CAMLparam5(prob, params, options, box, starts);
+  CAMLxparam2(x_out, values);
+  struct caml_ba_array* ba = Caml_ba_array_val(starts);
+  gprhip_problem* p = Problem_val(prob);
+  const double* x = (const double*)ba->data;
+  int64_t ld = ba->dim[0], ns = ba->dim[1];
+  const double* par = (const double*)Caml_ba_data_val(params);
+  const double* o = (const double*)Caml_ba_data_val(options);
+  const double* b = (const double*)Caml_ba_data_val(box);
+  double* xo = (double*)Caml_ba_data_val(x_out);
+  double* a = (double*)Caml_ba_data_val(values);
+  gprhip_acquisition acq;
+  gprhip_refine_options opt;
+  int status;
+  if (Caml_ba_array_val(params)->dim[0] != 7) caml_invalid_argument("Gpr_hip.acquire_refine: seven parameters");
+  if (Caml_ba_array_val(options)->dim[0] != 6) caml_invalid_argument("Gpr_hip.acquire_refine: six options");
+  if (Caml_ba_array_val(box)->dim[0] != ld || Caml_ba_array_val(box)->dim[1] != 2)
+    caml_invalid_argument("Gpr_hip.acquire_refine: the box is D x 2");
+  if (Caml_ba_array_val(x_out)->dim[0] != ld || Caml_ba_array_val(x_out)->dim[1] != ns ||
+      Caml_ba_array_val(values)->dim[0] != ns)
+    caml_invalid_argument("Gpr_hip.acquire_refine: x_out is D x ns, values ns");
+  acq.kind = (int)par[0];
+  acq.maximise = par[1] != 0.0;
+  acq.predictive = par[2] != 0.0;
+  acq.best = par[3];
+  acq.xi = par[4];
+  acq.kappa = par[5];
+  acq.var_floor = par[6];
+  opt.max_evals = (int)o[0];
+  opt.step0 = o[1];
+  opt.c1 = o[2];
+  opt.shrink = o[3];
+  opt.grow = o[4];
+  opt.xtol = o[5];
+  caml_release_runtime_system();
+  status = gprhip_acquire_refine(p, &acq, &opt, b, b + ld, NULL, x, ld, ns, xo, ld, a, NULL, ld, NULL, NULL, NULL, NULL, 0);
+  caml_acquire_runtime_system();
+  check(status);
+  CAMLreturn(Val_unit);
+}
+CAMLprim value gprhip_ml_acquire_refine_bc(value* argv, int argn) {
+  (void)argn;
+  return gprhip_ml_acquire_refine(argv[0], argv[1], argv[2], argv[3], argv[4], argv[5], argv[6]);
+}
+
 /* external sample_paths : problem -> z:mat -> points:mat -> eps:mat option -> samples:mat -> unit
  *   posterior sample paths at the points (nt x ns): column j is the draw fixed by column j of z (m x ns standard normal
  *   draws); with eps (nt x ns) the independent residual part is added, without it the path part alone is returned */

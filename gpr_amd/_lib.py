@@ -95,6 +95,23 @@ class Acquisition(C.Structure):
 
 
 ACQ_EI, ACQ_LOG_EI, ACQ_PI, ACQ_BOUND = range(4)
+
+
+class RefineOptions(C.Structure):
+    """gprhip_refine_options: the step rule's constants of gprhip_acquire_refine (include/gprhip.h)."""
+    _fields_ = [
+        ("max_evals", C.c_int),
+        ("step0", C.c_double),
+        ("c1", C.c_double),
+        ("shrink", C.c_double),
+        ("grow", C.c_double),
+        ("xtol", C.c_double),
+    ]
+
+
+REFINE_ST_CONVERGED, REFINE_ST_MAX_EVALS, REFINE_ST_NAN = range(3)
+REFINE_MAX_EVALS = 1000   # GPRHIP_REFINE_MAX_EVALS
+REFINE_MAX_STARTS = 4096  # GPRHIP_REFINE_MAX_STARTS
 MAX_TOP_K = 64    # GPRHIP_MAX_TOP_K
 MAX_DRAWS = 64    # GPRHIP_MAX_DRAWS
 MAX_TARGETS = 16  # GPRHIP_MAX_TARGETS
@@ -134,6 +151,8 @@ SIGNATURES = {
     "gprhip_predict_input_grad": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, _vp, _vp, _vp, _vp, C.c_int64, C.c_int]),
     "gprhip_acquire": (C.c_int, [_vp, C.POINTER(Acquisition), _vp, C.c_int64, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, C.c_int,
                                  C.POINTER(C.c_int64), _dp, _dp, C.c_int]),
+    "gprhip_acquire_refine": (C.c_int, [_vp, C.POINTER(Acquisition), C.POINTER(RefineOptions), _dp, _dp, _dp, _vp, C.c_int64, C.c_int64,
+                                        _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int]),
     "gprhip_sample_paths": (C.c_int, [_vp, _dp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int, _vp, C.c_int64,
                                       C.c_int, C.c_int, C.POINTER(C.c_int64), _dp, _dp, C.c_int]),
     "gprhip_predict_targets": (C.c_int, [_vp, _dp, C.c_int64, C.c_int64, _dp]),

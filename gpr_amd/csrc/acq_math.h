@@ -13,7 +13,8 @@
 //     g = 1 - x R(x).  That difference is taken as it stands for x < 5 (g(5) = 0.036: at most the factor 1 + u^2 that the
 //     conditioning of Phi in u costs anyway); beyond, R and g come from Laplace's continued fraction
 //     R = 1 / (x + 1 / (x + 2 / (x + 3 / ...))), g = c / (x + c) with c = 1 / (x + 2 / (x + 3 / ...)): sums of positive terms;
-//   * log h(u) = -u^2 / 2 - log sqrt(2 pi) + log g for u < 0: finite and accurate where phi, and EI with it, underflows.
+//   * log h(u) = -u^2 / 2 - log sqrt(2 pi) + log g for u < 0: finite and accurate where phi, and EI with it, underflows;
+//   * PI's coefficients phi / sigma and u phi / (2 v) are taken from a scaled phi where phi itself is subnormal.
 #pragma once
 #include <math.h>
 
@@ -72,8 +73,16 @@ GPRHIP_ACQ_FN AcqPoint acq_point(int kind, double s, double best, double xi, dou
   double cv;
   if (kind == ACQ_PI) {
     o.a = 0.5 * erfc(-0.70710678118654752440 * u);
-    o.cmu = s * phi / sigma;
-    cv = -u * phi / (2.0 * v);
+    if (phi < 2.2250738585072014e-308) {
+      // phi is subnormal (or 0) for |u| > 37.6, yet its quotients by sigma and by v need not be and must not inherit its
+      // few bits: they are formed from 2^128 phi and scaled back, one rounding into the subnormal range at the end
+      const double phs = inv_sqrt_2pi * exp(-0.5 * u * u + 88.722839111672999);  // 128 log 2
+      o.cmu = s * ldexp(phs / sigma, -128);
+      cv = ldexp(-u * phs / (2.0 * v), -128);
+    } else {
+      o.cmu = s * phi / sigma;
+      cv = -u * phi / (2.0 * v);
+    }
   } else if (u < 0.0) {
     double R, g;
     acq_mills(-u, R, g);

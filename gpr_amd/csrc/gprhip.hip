@@ -284,6 +284,11 @@ struct gprhip_problem {
   // device and its pinned mirror; made at the first call with top_k > 0
   void* acq_scratch = nullptr;
   double *acq_out = nullptr, *acq_host = nullptr;
+  // gprhip_acquire_refine: one arena for the box, the state and trial points of the starts and the staging of host outputs
+  // (rf_len doubles; grown when a call needs more), and the pinned count of starts that go on
+  double* rf_buf = nullptr;
+  int64_t rf_len = 0;
+  int* rf_active = nullptr;
   // gprhip_sample_paths: the normal draws Z [mp][64] in pinned host memory that the weight kernel reads, R~^-1 Z and the
   // weights A (2 [mp][64]); F / eps of one chunk ([64][sp_rows] each, made when a call needs them); the selection's
   // candidate lists and the winners' blocks [64][64 (D + 2)] with their pinned mirror
@@ -2284,6 +2289,110 @@ void do_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const double* 
   if (p->timer.on) tcollect(p);
 }
 
+// gprhip_acquire_refine: projected gradient ascent with Armijo backtracking from ns starts (refine_step.h is the rule).
+//   * at most 64 inducing points of at most 16 dimensions, no projection: one persistent kernel (refine.hip) -- the loop runs
+//     on the device;
+//   * every other shape: the loop runs here.  State and trial points stay in device buffers, an evaluation is the chunk walk
+//     of gprhip_acquire on them (ns fits one chunk), refine_step_kernel follows it and leaves the number of starts that go on
+//     in pinned memory: one integer per evaluation comes back.
+// The caller has checked the arguments and the model state; hs: the starts on the host, [ns][D], finite.
+void do_acquire_refine(gprhip_problem* p, const gprhip_acquisition* acq, const gprhip_refine_options* opt, const double* lower,
+                       const double* upper, const double* scale, const double* starts, std::vector<double>& hs, int64_t ns,
+                       double* x_out, int64_t ldx, double* values, double* dvalues, int64_t ldg, int* evals, int* accepted,
+                       int* status, double* trace, int on_device) {
+  const char* const fn = "gprhip_acquire_refine";
+  const bool want_var = !(acq->kind == GPRHIP_ACQ_BOUND && acq->kappa == 0.0);
+  GPR_HIP(hipSetDevice(p->device));
+  hipStream_t s = p->stream;
+  const int D = p->D;
+  const bool small = one_kernel_path(p) && !p->has_proj();
+  const int64_t rec = 2 * D + 3, nsD = ns * D;
+  const int64_t trace_len = (trace && !on_device) ? ns * opt->max_evals * rec : 0;
+  const int64_t len = 3 * D + 4 * nsD + 3 * ns + (3 * ns + 1) / 2 + trace_len;
+  const bool grow = p->rf_len < len;
+  const PgPlan plan = pg_prepare(p, fn, ns, want_var, false, true, grow ? len * 8 : 0);
+  if (grow) {
+    GPR_HIP(hipStreamSynchronize(s));
+    release_buf(p, p->rf_buf);
+    p->rf_len = 0;
+    p->rf_buf = p->alloc<double>(len);
+    p->rf_len = len;
+  }
+  if (!p->rf_active) GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->rf_active), sizeof(int), hipHostMallocDefault));
+  double* const bnd = p->rf_buf;
+  double *const Y = bnd + 3 * D, *const X = Y + nsD, *const G = X + nsD, *const GY = G + nsD;
+  double *const A = GY + nsD, *const AY = A + ns, *const AL = AY + ns;
+  int* const ints = reinterpret_cast<int*>(AL + ns);
+  double* const trace_dev = trace ? (on_device ? trace : AL + ns + (3 * ns + 1) / 2) : nullptr;
+  GPR_HIP(hipMemcpyAsync(bnd, lower, (size_t)D * 8, hipMemcpyHostToDevice, s));
+  GPR_HIP(hipMemcpyAsync(bnd + D, upper, (size_t)D * 8, hipMemcpyHostToDevice, s));
+  if (scale) GPR_HIP(hipMemcpyAsync(bnd + 2 * D, scale, (size_t)D * 8, hipMemcpyHostToDevice, s));
+  if (trace && !on_device)  // records that no evaluation writes keep what the caller's buffer holds
+    GPR_HIP(hipMemcpyAsync(trace_dev, trace, (size_t)trace_len * 8, hipMemcpyHostToDevice, s));
+  RefineOpts o;
+  o.max_evals = opt->max_evals; o.step0 = opt->step0; o.c1 = opt->c1; o.shrink = opt->shrink; o.grow = opt->grow;
+  o.xtol = opt->xtol;
+  AcqArgs q;
+  q.kind = acq->kind; q.s = acq->maximise ? 1.0 : -1.0; q.best = acq->best; q.xi = acq->xi; q.kappa = acq->kappa;
+  q.var_floor = acq->var_floor; q.values = nullptr;
+  const double add = acq->predictive ? p->h.sigma2 : 0.0;
+  if (small) {
+    const bool direct = on_device != 0;  // the kernel reads and writes the caller's device buffers
+    if (!direct) GPR_HIP(hipMemcpyAsync(Y, hs.data(), (size_t)nsD * 8, hipMemcpyHostToDevice, s));
+    SmallPredictGradArgs a{};
+    a.cp = p->cp; a.pts = direct ? starts : Y; a.Z = p->Z; a.shift = p->zshift; a.uinv = p->uinv; a.rinv = p->rinv;
+    a.tvec = p->tvec; a.rows = (int)ns; a.m = p->m; a.mp = p->mp; a.d = p->d; a.want_var = want_var ? 1 : 0; a.add = add;
+    SmallRefineArgs rf;
+    rf.lower = bnd; rf.upper = bnd + D; rf.scale = scale ? bnd + 2 * D : nullptr; rf.o = o;
+    rf.x_out = direct ? x_out : (x_out ? X : nullptr);
+    rf.values = direct ? values : (values ? A : nullptr);
+    rf.dvalues = direct ? dvalues : (dvalues ? G : nullptr);
+    rf.evals = direct ? evals : (evals ? ints : nullptr);
+    rf.accepted = direct ? accepted : (accepted ? ints + ns : nullptr);
+    rf.status = direct ? status : (status ? ints + 2 * ns : nullptr);
+    rf.trace = trace_dev;
+    tstart(p, "rf_small");
+    launch_small_refine(a, q, rf, s);
+    tstop(p);
+  } else {
+    for (int64_t i = 0; i < nsD; ++i) hs[i] = refine_clip(hs[i], lower[i % D], upper[i % D]);
+    GPR_HIP(hipMemcpyAsync(Y, hs.data(), (size_t)nsD * 8, hipMemcpyHostToDevice, s));
+    if (plan.mats) ensure_predict_m(p);
+    RefineStepArgs st;
+    st.ns = (int)ns; st.D = D; st.lower = bnd; st.upper = bnd + D; st.scale = scale ? bnd + 2 * D : nullptr; st.o = o;
+    st.x = X; st.g = G; st.y = Y; st.gy = GY; st.ay = AY; st.a = A; st.alpha = AL;
+    st.evals = ints; st.accepted = ints + ns; st.status = ints + 2 * ns; st.trace = trace_dev; st.active = p->rf_active;
+    q.values = AY;
+    for (int ev = 0; ev < o.max_evals; ++ev) {
+      st.first = ev == 0;
+      walk_chunks(p, plan.chunk, Y, D, ns, 1, [&](int64_t, int rows, int rows_p, const double*, const double* pts) {
+        double* const dsts[2] = {GY, nullptr};
+        pg_chunk(p, plan, pts, rows, rows_p, want_var, add, nullptr, nullptr, dsts, &q);
+        tstart(p, "rf_step");
+        launch_refine_step(st, s);
+        tstop(p);
+      });
+      if (*static_cast<volatile int*>(p->rf_active) == 0) break;
+    }
+  }
+  if (!(small && on_device)) {  // from the library's buffers to the caller's
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const double* const mats[2] = {X, G};
+    double* const dst[2] = {x_out, dvalues};
+    const int64_t lds[2] = {ldx, ldg};
+    for (int j = 0; j < 2; ++j)
+      if (dst[j])
+        GPR_HIP(hipMemcpy2DAsync(dst[j], (size_t)lds[j] * 8, mats[j], (size_t)D * 8, (size_t)D * 8, (size_t)ns, kind, s));
+    if (values) GPR_HIP(hipMemcpyAsync(values, A, (size_t)ns * 8, kind, s));
+    int* const idst[3] = {evals, accepted, status};
+    for (int j = 0; j < 3; ++j)
+      if (idst[j]) GPR_HIP(hipMemcpyAsync(idst[j], ints + j * ns, (size_t)ns * sizeof(int), kind, s));
+    if (trace && !on_device) GPR_HIP(hipMemcpyAsync(trace, trace_dev, (size_t)trace_len * 8, hipMemcpyDeviceToHost, s));
+  }
+  GPR_HIP(hipStreamSynchronize(s));
+  if (p->timer.on) tcollect(p);
+}
+
 // gprhip_sample_paths: ns draws of the posterior as functions, evaluated at nt test points chunk by chunk
 // (sample_paths.hip). The weights A = t 1^T + U^-1 (R~^-1 Z) are formed once per call; per chunk one kernel gives
 // F = K A (draw-major; K never reaches memory), with eps the residual standard deviation sqrt(max(0, sf2 - |K_r U^-1|^2 (+
@@ -3208,6 +3317,7 @@ void gprhip_problem_destroy(gprhip_problem* p) {
   if (p->hy_host && !p->is_lane) hipHostFree(p->hy_host);
   if (p->res_host) hipHostFree(p->res_host);
   if (p->acq_host) hipHostFree(p->acq_host);
+  if (p->rf_active) hipHostFree(p->rf_active);
   if (p->sp_zhost) hipHostFree(p->sp_zhost);
   if (p->sp_host) hipHostFree(p->sp_host);
   if (p->ev_fork) hipEventDestroy(p->ev_fork);
@@ -3652,30 +3762,24 @@ int gprhip_predict_input_grad(gprhip_problem* p, const double* test_inputs, int6
   }, p);
 }
 
+// what gprhip_acquire and gprhip_acquire_refine refuse of a criterion
+void check_acquisition(const char* fn, const gprhip_acquisition* acq) {
+  const char* why = nullptr;
+  if (!acq) why = "invalid arguments (acq is NULL)";
+  else if (acq->kind < GPRHIP_ACQ_EI || acq->kind > GPRHIP_ACQ_BOUND) why = "unknown kind (one of GPRHIP_ACQ_EI, _LOG_EI, _PI, _BOUND)";
+  else if (!(acq->xi >= 0.0) || !(acq->kappa >= 0.0)) why = "xi and kappa must not be negative";
+  else if (!(acq->var_floor > 0.0) || !std::isfinite(acq->var_floor)) why = "var_floor must be positive and finite";
+  else if (!std::isfinite(acq->best)) why = "best must be finite";
+  if (!why) return;
+  set_error(std::string(fn) + ": " + why);
+  throw HipFail{ST_BAD_ARG};
+}
+
 int gprhip_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const double* test_inputs, int64_t ld, int64_t nt,
                    double* values, double* dvalues, int64_t ldg, double* means, double* variances, int top_k,
                    int64_t* top_index, double* top_values, double* top_dvalues, int on_device) {
   return guarded([&] {
-    if (!acq) {
-      set_error("gprhip_acquire: invalid arguments (acq is NULL)");
-      throw HipFail{ST_BAD_ARG};
-    }
-    if (acq->kind < GPRHIP_ACQ_EI || acq->kind > GPRHIP_ACQ_BOUND) {
-      set_error("gprhip_acquire: unknown kind (one of GPRHIP_ACQ_EI, _LOG_EI, _PI, _BOUND)");
-      throw HipFail{ST_BAD_ARG};
-    }
-    if (!(acq->xi >= 0.0) || !(acq->kappa >= 0.0)) {
-      set_error("gprhip_acquire: xi and kappa must not be negative");
-      throw HipFail{ST_BAD_ARG};
-    }
-    if (!(acq->var_floor > 0.0) || !std::isfinite(acq->var_floor)) {
-      set_error("gprhip_acquire: var_floor must be positive and finite");
-      throw HipFail{ST_BAD_ARG};
-    }
-    if (!std::isfinite(acq->best)) {
-      set_error("gprhip_acquire: best must be finite");
-      throw HipFail{ST_BAD_ARG};
-    }
+    check_acquisition("gprhip_acquire", acq);
     if (top_k < 0 || top_k > GPRHIP_MAX_TOP_K) {
       set_error("gprhip_acquire: top_k must lie in 0 .. GPRHIP_MAX_TOP_K (64)");
       throw HipFail{ST_BAD_ARG};
@@ -3710,6 +3814,54 @@ int gprhip_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const doubl
     }
     do_acquire(p, acq, test_inputs, ld, nt, values, dvalues, ldg, means, variances, top_k, top_index, top_values, top_dvalues,
                on_device);
+  }, p);
+}
+
+int gprhip_acquire_refine(gprhip_problem* p, const gprhip_acquisition* acq, const gprhip_refine_options* opt, const double* lower,
+                          const double* upper, const double* scale, const double* starts, int64_t ld, int64_t ns, double* x_out,
+                          int64_t ldx, double* values, double* dvalues, int64_t ldg, int* evals, int* accepted, int* status,
+                          double* trace, int on_device) {
+  return guarded([&] {
+    const char* const fn = "gprhip_acquire_refine";
+    auto refuse = [&](const std::string& why) {
+      set_error(std::string(fn) + ": " + why);
+      throw HipFail{ST_BAD_ARG};
+    };
+    check_acquisition(fn, acq);
+    if (!opt) refuse("invalid arguments (opt is NULL)");
+    if (opt->max_evals < 1 || opt->max_evals > GPRHIP_REFINE_MAX_EVALS) refuse("max_evals must lie in 1 .. GPRHIP_REFINE_MAX_EVALS (1000)");
+    if (!(opt->step0 > 0.0 && opt->step0 <= 1.0)) refuse("step0 must lie in (0, 1]");
+    if (!(opt->c1 >= 0.0 && opt->c1 < 1.0)) refuse("c1 must lie in [0, 1)");
+    if (!(opt->shrink > 0.0 && opt->shrink < 1.0)) refuse("shrink must lie in (0, 1)");
+    if (!(opt->grow >= 1.0) || !std::isfinite(opt->grow)) refuse("grow must be finite and at least 1");
+    if (!(opt->xtol >= 0.0) || !std::isfinite(opt->xtol)) refuse("xtol must be finite and not negative");
+    if (ns < 1 || ns > GPRHIP_REFINE_MAX_STARTS) refuse("ns must lie in 1 .. GPRHIP_REFINE_MAX_STARTS (4096)");
+    if (!x_out && !values && !dvalues && !evals && !accepted && !status && !trace) refuse("nothing is requested (all outputs are NULL)");
+    if (!p || !starts || !lower || !upper) refuse("invalid arguments");
+    if (p->f32) refuse("the prediction gradient is evaluated in fp64 only (GPRHIP_F32_BULK problem)");
+    if (p->d > 64) refuse("at most 64 point dimensions on the kernel side (d)");
+    const int D = p->D;
+    if (on_device ? ld != D : ld < D) refuse("bad ld (need ld == D for device buffers, ld >= D for host buffers)");
+    if (x_out && (on_device ? ldx != D : ldx < D)) refuse("bad ldx (need ldx == D for device buffers, ldx >= D for host buffers)");
+    if (dvalues && (on_device ? ldg != D : ldg < D)) refuse("bad ldg (need ldg == D for device buffers, ldg >= D for host buffers)");
+    for (int k = 0; k < D; ++k) {
+      if (!std::isfinite(lower[k]) || !std::isfinite(upper[k]) || !(lower[k] < upper[k])) refuse("lower and upper must be finite with lower < upper");
+      if (scale && (!(scale[k] > 0.0) || !std::isfinite(scale[k]))) refuse("scale must be positive and finite");
+    }
+    // the model state before the starts are read back from the device: a refused call enqueues nothing
+    need_posterior_state(p, fn, "predict from", true, !(acq->kind == GPRHIP_ACQ_BOUND && acq->kappa == 0.0), true,
+                         "means and their gradients are available after the next gprhip_eval");
+    std::vector<double> hs((size_t)ns * D);
+    if (on_device) {
+      GPR_HIP(hipSetDevice(p->device));
+      GPR_HIP(hipMemcpy(hs.data(), starts, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
+    } else {
+      for (int64_t i = 0; i < ns; ++i) std::copy(starts + i * ld, starts + i * ld + D, hs.begin() + i * D);
+    }
+    for (double v : hs)
+      if (!std::isfinite(v)) refuse("the starts must be finite");
+    do_acquire_refine(p, acq, opt, lower, upper, scale, starts, hs, ns, x_out, ldx, values, dvalues, ldg, evals, accepted, status,
+                      trace, on_device);
   }, p);
 }
 

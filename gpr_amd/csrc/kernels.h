@@ -8,6 +8,7 @@
 //              (tile-granular: every 128x128 tile with row tile <= column tile is fully written)
 #pragma once
 #include "common.h"
+#include "refine_step.h"
 
 namespace gprhip {
 
@@ -342,6 +343,36 @@ struct AcqSelectManyArgs {
 };
 int64_t acq_select_many_scratch_bytes(int64_t rows, int k, int ncols);
 void launch_acq_select_many(const AcqSelectManyArgs& a, hipStream_t s);
+
+// ---- gprhip_acquire_refine (refine.hip): projected gradient ascent with Armijo backtracking from ns starts inside a box, by
+// the rule of refine_step.h.  Integer outputs are [ns]; the trace is [ns][max_evals][2 D + 3] records (y, g_y, a_y, alpha,
+// accepted), one per evaluation.
+struct SmallRefineArgs {
+  const double *lower, *upper, *scale;  // [d] (device); scale may be null: all ones
+  RefineOpts o;
+  double *x_out, *values, *dvalues;     // [ns][d], [ns], [ns][d]; each may be null
+  int *evals, *accepted, *status;       // each may be null
+  double* trace;                        // or null
+};
+// One persistent kernel for the shapes of launch_small_acquire_grad (m <= 64, d <= 16, no projection): a.pts are the ns = a.rows
+// starts, 64 per workgroup; U^-1, R~^-1, Z - s and t are staged once and the evaluation loop runs inside the kernel.  Of `a`,
+// means / vars / dmeans / dvars / ldg are not used.
+void launch_small_refine(const SmallPredictGradArgs& a, const AcqArgs& q, const SmallRefineArgs& rf, hipStream_t s);
+// The step of the library-side loop: one start per thread on [ns][D] device arrays.  first: (ay, gy) is the evaluation at the
+// clipped starts in y (x, g, st_* are initialised from it), else at the trial points y.  y receives the next trial points;
+// *active (pinned host memory, device-visible) the number of starts that go on.  One workgroup, no atomics.
+struct RefineStepArgs {
+  int ns, D, first;
+  const double *lower, *upper, *scale;  // [D] (device); scale may be null
+  RefineOpts o;
+  double *x, *g, *y;                    // [ns][D]
+  const double *gy, *ay;                // [ns][D], [ns]
+  double *a, *alpha;                    // [ns]
+  int *evals, *accepted, *status;       // [ns]
+  double* trace;                        // or null
+  int* active;
+};
+void launch_refine_step(const RefineStepArgs& a, hipStream_t s);
 
 // ---- posterior sample paths (sample_paths.hip): a draw is f(x) = sum_c k(x, z_c) a_c with the weights a = t + U^-1 R~^-1 z
 constexpr int SP_MAX_DRAWS = 64;  // GPRHIP_MAX_DRAWS, and the leading dimension of the m x ns weight matrices ([mp][64])

@@ -15,20 +15,11 @@
 //     V = K U^-1, Q = V R~^-1, H = V - Q R~^-T, G = H U^-T on the 64 x 64 corners, then both E products against Z - s.
 #include <type_traits>
 
-#include "kernels.h"
-#include "exp_fast.h"
-#include "acq_math.h"
+#include "small_pg.h"
 
 namespace gprhip {
 
 namespace {
-
-typedef double pd4 __attribute__((ext_vector_type(4)));
-typedef double pd2 __attribute__((ext_vector_type(2)));
-// lane supplies A[lane&15][lane>>4] and B[lane>>4][lane&15]; accumulator element r is D[(lane>>4) + 4r][lane&15]
-__device__ __forceinline__ pd4 pmfma4(double a, double b, pd4 c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 
 constexpr int PG_CP = 64;    // inducing columns per staged panel
 constexpr int PG_ROWS = 64;  // test points per workgroup
@@ -62,73 +53,22 @@ void launch_one_acq(const PredictGradArgs& a, const AcqArgs& q, hipStream_t s) {
   else hipLaunchKernelGGL((acquire_grad_kernel<KS4, DT, false>), grid, dim3(256), 0, s, a, q);
 }
 
-// ---- at most 64 inducing points of at most 16 dimensions: a block of 64 test points in one kernel
-constexpr int SM = 64;    // inducing points (padded)
-constexpr int SLD = 66;   // leading dimension of the 64 x 64 LDS matrices
-constexpr int SRB = 64;   // test points per workgroup
-constexpr int LDZ = 20;   // leading dimension of the staged Z - s (16 dimensions)
-
-// rows [16 wv, 16 wv + 16) of  A (LDS, [64][SLD]) times  B (LDS, [64][SLD]; TRANS: times B^T)  -> acc[ct], ct = column tile
-// (the fully unrolled form of small.hip's rows_times: all fragments of a half of the k-range loaded before its 32 MFMAs)
-template <bool TRANS>
-__device__ __forceinline__ void rows_times(const double* A, const double* B, int wv, int l15, int lq, pd4 (&acc)[4]) {
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct) acc[ct] = pd4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    double af[8], bf[8][4];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int kk = 8 * h + j;
-      af[j] = A[(16 * wv + l15) * SLD + 4 * kk + lq];
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct)
-        bf[j][ct] = TRANS ? B[(16 * ct + l15) * SLD + 4 * kk + lq] : B[(4 * kk + lq) * SLD + 16 * ct + l15];
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) acc[ct] = pmfma4(af[j], bf[j][ct], acc[ct]);
-  }
-}
-
-// 64 x 64 corner of a row-major mp x mp matrix -> LDS
-__device__ __forceinline__ void load_corner(const double* __restrict__ M, int mp, double* L, int tid) {
-  double2 v[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int idx = tid + 256 * j, r = idx >> 5, c2 = (idx & 31) * 2;
-    v[j] = *reinterpret_cast<const double2*>(M + (int64_t)r * mp + c2);
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int idx = tid + 256 * j, r = idx >> 5, c2 = (idx & 31) * 2;
-    *reinterpret_cast<double2*>(L + r * SLD + c2) = v[j];
-  }
-}
-
-// rows of this wavefront: accumulator tiles -> LDS (in place of an operand the wavefront alone reads)
-__device__ __forceinline__ void store_rows(double* W, const pd4 (&acc)[4], int wv, int l15, int lq) {
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) W[(16 * wv + lq + 4 * r) * SLD + 16 * ct + l15] = acc[ct][r];
-}
-
+// ---- at most 64 inducing points of at most 16 dimensions: a block of 64 test points in one kernel (small_pg.h has the
+// LDS shapes and the 64 x 64 products; REFINE: the body inside the loop of small_refine_kernel, refine.hip)
 // DT: padded point dimension of the direct-difference covariance (d <= DT)
 template <int DT>
 __global__ __launch_bounds__(256) void small_predict_grad_kernel(SmallPredictGradArgs a) {
-  constexpr bool ACQ = false;
+  constexpr bool ACQ = false, REFINE = false;
   const AcqArgs q{};
+  const SmallRefineArgs rf{};
 #include "small_predict_grad_body.inc"
 }
 template <int DT>
 __global__ __launch_bounds__(256) void small_acquire_grad_kernel(SmallPredictGradArgs a, AcqArgs q) {
-  constexpr bool ACQ = true;
+  constexpr bool ACQ = true, REFINE = false;
+  const SmallRefineArgs rf{};
 #include "small_predict_grad_body.inc"
 }
-
-size_t small_pg_lds(int DT) { return (size_t)(4 * SM * SLD + SM * LDZ + SRB * DT + SM + 16) * sizeof(double); }
 
 void small_pg_attrs() {
   static uint64_t done = 0;

@@ -25,12 +25,26 @@
   for (int idx = tid; idx < SRB * DT; idx += 256) {
     const int r = idx / DT, k = idx % DT;
     xs[idx] = (k < a.d && r0 + r < a.rows) ? a.pts[(int64_t)(r0 + r) * a.d + k] : 0.0;
+    if constexpr (REFINE)  // the starts, clipped into the box
+      if (k < a.d) xs[idx] = refine_clip(xs[idx], rf.lower[k], rf.upper[k]);
   }
   __syncthreads();
   for (int idx = tid; idx < SM * 16; idx += 256) {
     const int c = idx >> 4, k = idx & 15;
     zs[c * LDZ + k] = (c < a.m && k < a.d) ? a.Z[(int64_t)c * a.d + k] - sh[k] : 0.0;
   }
+  // REFINE: what follows is one evaluation at the points in xs, inside the loop of the rule (rf_step, small_pg.h); the trip
+  // count is the same for the whole workgroup
+  [[maybe_unused]] RefineRows rr;
+  [[maybe_unused]] bool rf_first = true, rf_more = false;
+  if constexpr (REFINE) {
+    const bool comp = l15 < a.d;
+    rr.lo = comp ? rf.lower[l15] : 0.0;
+    rr.hi = comp ? rf.upper[l15] : 0.0;
+    rr.w = comp ? rr.hi - rr.lo : INFINITY;
+    rr.sc = (comp && rf.scale) ? rf.scale[l15] : 1.0;
+  }
+  do {
 #pragma unroll 4
   for (int i = 0; i < 16; ++i) {
     const int r = wv * 16 + i;
@@ -100,18 +114,24 @@
       c.cmu = q.s;
       c.cv = 0.0;
     }
-    if (lq == 0 && prow < a.rows && q.values) q.values[prow] = c.a;
+    if constexpr (!REFINE)
+      if (lq == 0 && prow < a.rows && q.values) q.values[prow] = c.a;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int lrow = 16 * wv + lq + 4 * r, orow = r0 + lrow;
       const double rm = __shfl(rsm, lq + 4 * r), rv = __shfl(rsv, lq + 4 * r);
       const double cm = __shfl(c.cmu, lq + 4 * r), cv = __shfl(c.cv, lq + 4 * r);
-      if (orow < a.rows && l15 < a.d && a.dmeans) {
+      if constexpr (REFINE) {
+        rr.ay[r] = __shfl(c.a, lq + 4 * r);
+        rr.gy[r] = 0.0;
+      }
+      if (orow < a.rows && l15 < a.d && (REFINE || a.dmeans)) {
         const double pc = xs[lrow * DT + l15] - sh[l15];
         const double dm = -inv_ell2 * (pc * rm - am[r]);  // the entries the plain kernel stores
         double g = cm * dm;
         if (var) g += cv * (2.0 * inv_ell2 * (pc * rv - av[r]));
-        a.dmeans[(int64_t)orow * a.ldg + l15] = g;
+        if constexpr (REFINE) rr.gy[r] = g;
+        else a.dmeans[(int64_t)orow * a.ldg + l15] = g;
       }
     }
   } else {
@@ -126,3 +146,9 @@
       }
     }
   }
+  if constexpr (REFINE) {
+    rf_more = __syncthreads_or(rf_step<DT>(a, rf, rr, xs, r0, wv, lq, l15, rf_first) ? 1 : 0) != 0;
+    rf_first = false;
+  }
+  } while (REFINE && rf_more);
+  if constexpr (REFINE) rf_store(a, rf, rr, r0, wv, lq, l15);

@@ -336,6 +336,70 @@ class Problem:
             out.update(top_index=top_index, top_values=top_values, top_dvalues=top_dvalues)
         return out
 
+    REFINE_OUTPUTS = ("x", "values", "dvalues", "evals", "accepted", "status", "trace")
+
+    def acquire_refine(self, starts, kind, *, lower, upper, maximise, scale=None, best=0.0, xi=0.0, kappa=0.0, var_floor=None,
+                       predictive=False, max_evals=50, step0=0.1, c1=1e-4, shrink=0.5, grow=2.0, xtol=1e-8,
+                       want=("x", "values", "dvalues", "evals", "accepted", "status"), out_device_ptrs=None, ns=None):
+        """Refines candidates of an acquisition criterion on the device (gprhip_acquire_refine): projected gradient ascent with
+        Armijo backtracking from the columns of `starts` (D x ns) inside the box [lower, upper] (D each), every start on its
+        own.  kind and the criterion's keywords as `acquire`; scale (D, default ones) weights the gradient's components;
+        max_evals / step0 / c1 / shrink / grow / xtol are the rule's constants (include/gprhip.h).  Returns a dict with the
+        names in `want`: x (D x ns), values [ns] and dvalues (D x ns) -- value and gradient at x --, evals / accepted / status
+        [ns] (int32; status one of _lib.REFINE_ST_*), trace [ns, max_evals, 2 D + 3] with one record (y, g_y, a_y, alpha,
+        accepted) per evaluation and NaN where none was made.
+        out_device_ptrs: {name: device address} for the names in `want` (x / dvalues point-major [ns][D], the integers int32,
+        trace as above); `starts` is then the device address of a contiguous point-major [ns][D] fp64 array of `ns` points,
+        the outputs are written in place and {} is returned."""
+        want = tuple(want)
+        unknown = [w for w in want if w not in self.REFINE_OUTPUTS]
+        if unknown:
+            raise ValueError("acquire_refine: unknown outputs %s" % unknown)
+        if isinstance(kind, str):
+            if kind not in self.ACQUIRE_KINDS:
+                raise ValueError("acquire_refine: unknown kind %r (one of %s)" % (kind, sorted(self.ACQUIRE_KINDS)))
+            kind = self.ACQUIRE_KINDS[kind]
+        if var_floor is None:
+            if getattr(self, "_log_sf2", None) is None:
+                raise ValueError("acquire_refine: var_floor is needed (this object has not seen the model state's log_sf2)")
+            var_floor = 1e-10 * float(np.exp(self._log_sf2))
+        acq = _lib.Acquisition(int(kind), int(bool(maximise)), int(bool(predictive)), float(best), float(xi), float(kappa),
+                               float(var_floor))
+        opt = _lib.RefineOptions(int(max_evals), float(step0), float(c1), float(shrink), float(grow), float(xtol))
+        box = [np.ascontiguousarray(b, dtype=np.float64) for b in (lower, upper)]
+        if scale is not None:
+            box.append(np.ascontiguousarray(scale, dtype=np.float64))
+        if any(b.shape != (self.D,) for b in box):
+            raise ValueError("acquire_refine: lower, upper and scale take %d entries each" % self.D)
+        bptr = [_f64_ptr(b) for b in box] + ([None] if scale is None else [])
+        null = C.c_void_p(None)
+        out = {}
+        if out_device_ptrs is not None:
+            if ns is None:
+                raise ValueError("acquire_refine: device buffers need ns")
+            ptrs = {w: (C.c_void_p(int(out_device_ptrs[w])) if w in want else null) for w in self.REFINE_OUTPUTS}
+            st_ptr, on_device, ns = C.c_void_p(int(starts)), 1, int(ns)
+        else:
+            xs = np.asfortranarray(starts, dtype=np.float64)
+            if xs.ndim != 2 or xs.shape[0] != self.D:
+                raise ValueError("acquire_refine: expected starts of shape (%d, ns)" % self.D)
+            ns = xs.shape[1]
+            for w in want:
+                if w in ("x", "dvalues"):
+                    out[w] = np.full((self.D, ns), np.nan, dtype=np.float64, order="F")
+                elif w == "values":
+                    out[w] = np.full(ns, np.nan, dtype=np.float64)
+                elif w == "trace":
+                    out[w] = np.full((ns, int(max_evals), 2 * self.D + 3), np.nan, dtype=np.float64)
+                else:
+                    out[w] = np.full(ns, -1, dtype=np.int32)
+            ptrs = {w: (C.c_void_p(out[w].ctypes.data) if w in out else null) for w in self.REFINE_OUTPUTS}
+            st_ptr, on_device = C.c_void_p(xs.ctypes.data), 0
+        _lib.check(self._lib.gprhip_acquire_refine(self._handle(), C.byref(acq), C.byref(opt), *bptr, st_ptr, self.D, ns,
+                                                   ptrs["x"], self.D, ptrs["values"], ptrs["dvalues"], self.D, ptrs["evals"],
+                                                   ptrs["accepted"], ptrs["status"], ptrs["trace"], on_device))
+        return out
+
     def sample_paths(self, test_inputs, z, eps=None, predictive=False, maximise=True, top_k=0, want_samples=True,
                      out_device_ptrs=None, nt=None):
         """Posterior sample paths at test points (gprhip_sample_paths).  z: m x ns standard normal draws (host, 1 <= ns <= 64);

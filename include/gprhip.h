@@ -406,6 +406,57 @@ int gprhip_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const doubl
                    double* values, double* dvalues, int64_t ldg, double* means, double* variances, int top_k,
                    int64_t* top_index, double* top_values, double* top_dvalues, int on_device);
 
+/* Refines candidates of an acquisition criterion on the device: projected gradient ascent with Armijo backtracking from ns
+ * starting points inside a box, every start on its own -- what follows gprhip_acquire's top_k when the maximiser is wanted and
+ * not the best grid point (an extension beyond the reference's implemented surface).  The criterion is any gprhip_acquisition,
+ * its value a and gradient g those of gprhip_acquire.  With w_k = upper_k - lower_k, per start:
+ *   1. x = clip(start); (a, g) at x; evals = 1.  a NaN: status GPRHIP_REFINE_ST_NAN.
+ *   2. dir_k = scale_k g_k, set to 0 where the bound is active and dir_k points out of the box (and where g_k is NaN).  All
+ *      dir_k == 0: GPRHIP_REFINE_ST_CONVERGED.  Otherwise alpha = (step0 min_k w_k) / max_k |dir_k|.
+ *   3. While evals < max_evals:  y = clip(x + alpha dir) (y_k = x_k where dir_k == 0), delta = y - x.  If
+ *      max_k |delta_k| / w_k <= xtol: CONVERGED.  Otherwise (a_y, g_y) at y, ++evals.  If a_y >= a + c1 sum_k g_k delta_k (false
+ *      for NaN): accept -- x, a, g = y, a_y, g_y, ++accepted, dir again (all zero: CONVERGED), alpha *= grow.  Else
+ *      alpha *= shrink.
+ *   4. GPRHIP_REFINE_ST_MAX_EVALS when the evaluations run out.
+ * lower / upper / scale: HOST always, D doubles each; scale == NULL means all ones.
+ * Outputs per start, each may be NULL: x_out (D), values and dvalues (D) -- the value and gradient at x_out from the evaluation
+ * that produced it, there is no extra evaluation --, evals, accepted, status (int), and trace, [ns][max_evals][2 D + 3] doubles
+ * in either mode: evaluation j of a start writes record j = (y, g_y, a_y, alpha, accepted as 0 / 1); record 0 is the clipped
+ * start with alpha = 0 and accepted = 1; records after the last evaluation are left untouched.
+ *   on_device = 0: starts (Fortran D x ns, ld >= D), x_out (D x ns, ldx >= D), dvalues (D x ns, ldg >= D; rows beyond D left
+ *                  untouched), values / evals / accepted / status (ns) and trace are host buffers.
+ *   on_device = 1: they are device pointers on the problem's device, starts / x_out / dvalues point-major [ns][D],
+ *                  ld == ldx == ldg == D; the starts are read back once to be checked.
+ * Two routes, one rule.  At most 64 inducing points of at most 16 dimensions without a projection: ONE persistent kernel, 64
+ * starts per workgroup, the model in LDS and the loop on the device.  Every other shape gprhip_acquire accepts: the loop runs in
+ * the library on device buffers -- an evaluation is gprhip_acquire's chunk walk, a step kernel follows, and one integer (the
+ * number of starts that go on) comes back per evaluation.  A start's result does not depend on the other starts; two runs give
+ * the same bits.
+ * GPRHIP_EBADARG: everything gprhip_acquire refuses of the criterion; max_evals outside 1 .. GPRHIP_REFINE_MAX_EVALS, step0
+ * outside (0, 1], c1 outside [0, 1), shrink outside (0, 1), grow < 1, xtol < 0 (or any of them not finite); scale not positive and
+ * finite; lower >= upper or non-finite bounds; a non-finite start; ns outside 1 .. GPRHIP_REFINE_MAX_STARTS; all outputs NULL;
+ * bad ld / ldx / ldg.  State and limits: as gprhip_acquire (GPRHIP_ESTATE under the same conditions; BOUND with kappa == 0 runs
+ * the mean part alone and needs no factors).  New buffers are checked against the free device memory first (GPRHIP_EOOM).  A
+ * refused call enqueues nothing; the call never changes the predictor state.
+ * Limits: no optimiser other than this one (no L-BFGS, no q-batch criteria); drawn sample paths are not refined; fp64 problems,
+ * one device, no multiscales.
+ * Stage timers: "rf_small" (the persistent kernel); on the other route those of gprhip_acquire per evaluation and "rf_step". */
+enum { GPRHIP_REFINE_ST_CONVERGED = 0, GPRHIP_REFINE_ST_MAX_EVALS = 1, GPRHIP_REFINE_ST_NAN = 2 };
+#define GPRHIP_REFINE_MAX_EVALS 1000
+#define GPRHIP_REFINE_MAX_STARTS 4096
+typedef struct {
+  int max_evals;  /* 1 .. GPRHIP_REFINE_MAX_EVALS: evaluations per start, the one at the start included */
+  double step0;   /* (0, 1]: the first step moves the fastest component by step0 times the narrowest width */
+  double c1;      /* [0, 1): Armijo's sufficient-increase constant */
+  double shrink;  /* (0, 1): step factor after a rejected trial */
+  double grow;    /* >= 1: step factor after an accepted trial */
+  double xtol;    /* >= 0: a trial step below xtol of the box widths ends the start */
+} gprhip_refine_options;
+int gprhip_acquire_refine(gprhip_problem* p, const gprhip_acquisition* acq, const gprhip_refine_options* opt, const double* lower,
+                          const double* upper, const double* scale, const double* starts, int64_t ld, int64_t ns, double* x_out,
+                          int64_t ldx, double* values, double* dvalues, int64_t ldg, int* evals, int* accepted, int* status,
+                          double* trace, int on_device);
+
 /* Posterior sample paths over test points, with the best top_k points of every draw -- Thompson sampling, batch selection by
  * independent draws, posterior pictures over a grid (an extension beyond the reference's implemented surface; its Cov_sampler
  * forms and factors an nt x nt covariance).  The FITC posterior is a Gaussian over m weights, so a draw is a FUNCTION of x,

@@ -725,6 +725,12 @@ struct Make_deriv {
       Vec top_values;
       Mat top_dvalues;
     };
+    struct Refined_t {
+      Mat x;         // D x ns
+      Vec values;    // value and gradient at x
+      Mat dvalues;
+      std::vector<int> evals, accepted, status;
+    };
     struct Acquisition {
       static Acquired_t calc(const Trained_t& trained, const Inputs_t& in, const gprhip_acquisition& acq, int top_k = 0) {
         Problem& p = problem_for(trained, in, "Acquisition.calc");
@@ -735,6 +741,22 @@ struct Make_deriv {
                              a.dvalues.data(), in.points->rows, nullptr, nullptr, top_k, k ? a.top_index.data() : nullptr,
                              k ? a.top_values.data() : nullptr, k ? a.top_dvalues.data() : nullptr, 0));
         return a;
+      }
+      // The starts (D x ns, in.points) refined inside the box [lower, upper] by projected gradient ascent with Armijo
+      // backtracking (gprhip_acquire_refine); scale: nullptr for all ones.  status holds GPRHIP_REFINE_ST_* per start.
+      static Refined_t refine(const Trained_t& trained, const Inputs_t& in, const gprhip_acquisition& acq,
+                              const gprhip_refine_options& opt, const Vec& lower, const Vec& upper, const Vec* scale = nullptr) {
+        Problem& p = problem_for(trained, in, "Acquisition.refine");
+        const size_t D = (size_t)in.points->rows, ns = (size_t)in.points->cols;
+        if (lower.size() != D || upper.size() != D || (scale && scale->size() != D))
+          throw std::invalid_argument("Acquisition.refine: lower, upper and scale take D entries each");
+        Refined_t r{Mat(in.points->rows, in.points->cols), Vec(ns), Mat(in.points->rows, in.points->cols), std::vector<int>(ns),
+                    std::vector<int>(ns), std::vector<int>(ns)};
+        check(gprhip_acquire_refine(p.get(), &acq, &opt, lower.data(), upper.data(), scale ? scale->data() : nullptr,
+                                    in.points->data(), in.points->rows, in.points->cols, r.x.data(), in.points->rows,
+                                    r.values.data(), r.dvalues.data(), in.points->rows, r.evals.data(), r.accepted.data(),
+                                    r.status.data(), nullptr, 0));
+        return r;
       }
     };
     // Posterior sample paths (gprhip_sample_paths: an extension beyond the reference's implemented surface).  A sampler keeps

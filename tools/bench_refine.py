@@ -1,0 +1,84 @@
+"""Cost of refining candidates on the device: Problem.acquire_refine on device pointers against the floor of any host-driven
+loop -- `evals` times one Problem.acquire call (values + gradient, device pointers) over the same ns points -- timed INTERLEAVED
+in one process on one device: host wall time of the blocking calls, median of REPS after two warm-ups.  Shapes: n = 2000 / m = 50
+(d = 3) with 64 and 1024 starts (the persistent kernel), n = 10 000 / m = 256 and n = 100 000 / m = 2048 (d = 8) with 64 starts
+(the library-side loop).  `evals` of a refine call is its largest per-start evaluation count -- the number of evaluations the
+loop made; the yardstick runs that many acquire calls (the parent commit's kernels but for PI's coefficients where phi is
+subnormal, acq_math.h; log EI, timed here, is instruction for instruction the parent's).  Then the HIP-event stage times
+(timing level 2) of one refine call.  Every line of the output file is written by this tool.
+    usage (GPU box, repo root): timeout 900 python3 tools/bench_refine.py [--out profiles/refine_cost.txt] [--skip-big]
+"""
+import os
+import sys
+import time
+
+import numpy as np
+
+import torch  # noqa: F401  (first: one HIP runtime serves both)
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import gpr_amd  # noqa: E402
+from bench import synth  # noqa: E402
+
+REPS = int(os.environ.get("REPS", 7))
+MAX_EVALS = 40
+out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
+shapes = [("n=2000 m=50", 2000, 50, 3, 64), ("n=2000 m=50", 2000, 50, 3, 1024), ("n=10000 m=256", 10000, 256, 8, 64)]
+if "--skip-big" not in sys.argv:
+    shapes += [("n=100000 m=2048", 100000, 2048, 8, 64)]
+lines = ["# tools/bench_refine.py: acquire_refine (log EI, max_evals %d) vs evals x acquire, device pointers, interleaved, host wall" % MAX_EVALS,
+         "# time in ms (median of %d after 2 warm-ups); per eval: the call over its evaluations; stages: HIP events (timing level 2) of" % REPS,
+         "# one refine call, summed over its evaluations",
+         "%-16s %6s %6s %10s %12s %10s %12s %7s   %s" % ("shape", "ns", "evals", "refine", "refine/eval", "loop", "acquire/call", "ratio",
+                                                        "stages (ms)")]
+dev = "cuda:0"
+for name, n, m, d, ns in shapes:
+    X, y, Z = synth(1, n, m, d)
+    kw = dict(log_ell=0.5 * np.log(d), log_sf2=0.0, sigma2=0.1, inducing=Z)
+    p = gpr_amd.Problem(gpr_amd.COV_SE_ISO, n, d, d, m)
+    p.set_inputs(X)
+    p.set_targets(y)
+    p.eval(want_grad=False, **kw)
+    rng = np.random.default_rng(2)
+    S = rng.normal(size=(ns, d))
+    lo, hi = np.full(d, -3.0), np.full(d, 3.0)
+    st = torch.tensor(np.ascontiguousarray(np.clip(S, -3.0, 3.0)), device=dev)
+    outs = {"x": torch.empty((ns, d), dtype=torch.float64, device=dev), "values": torch.empty(ns, dtype=torch.float64, device=dev),
+            "dvalues": torch.empty((ns, d), dtype=torch.float64, device=dev), "evals": torch.empty(ns, dtype=torch.int32, device=dev),
+            "status": torch.empty(ns, dtype=torch.int32, device=dev)}
+    ptrs = {k: v.data_ptr() for k, v in outs.items()}
+    acq = dict(maximise=False, best=float(np.min(y)), xi=0.01)
+    torch.cuda.synchronize()
+
+    def refine():
+        p.acquire_refine(st.data_ptr(), "log_ei", lower=lo, upper=hi, max_evals=MAX_EVALS, want=tuple(ptrs), out_device_ptrs=ptrs,
+                         ns=ns, **acq)
+
+    refine()
+    evals = int(outs["evals"].max().item())
+    aptr = {"values": ptrs["values"], "dvalues": ptrs["dvalues"]}
+
+    def loop():
+        for _ in range(evals):
+            p.acquire(st.data_ptr(), "log_ei", out_device_ptrs=aptr, nt=ns, **acq)
+
+    times = [[], []]
+    for _ in range(REPS + 2):
+        for t, f in zip(times, (refine, loop)):
+            t0 = time.perf_counter()
+            f()
+            t.append(time.perf_counter() - t0)
+    tr, tl = (1e3 * float(np.median(t[2:])) for t in times)
+    p.set_timing(2)
+    refine()
+    stg = p.last_timings()
+    p.set_timing(0)
+    stages = "  ".join("%s %.3f" % (k, v) for k, v in stg.items() if k.startswith(("pg_", "rf_")))
+    lines.append("%-16s %6d %6d %10.3f %12.4f %10.3f %12.4f %7.2f   %s" % (name, ns, evals, tr, tr / evals, tl, tl / evals, tr / tl, stages))
+    print(lines[-1], flush=True)
+    p.close()
+    del outs, st, X, y, Z
+text = "\n".join(lines) + "\n"
+if out_path:
+    with open(out_path, "w") as f:
+        f.write(text)

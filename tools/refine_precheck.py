@@ -1,0 +1,54 @@
+"""The seeds of tests/test_gpu_refine.py's trace cases, checked on the CPU before the device sees them: tests/refine_ref.py over
+the 80-bit evaluator of tests/refine_cases.py (longdouble posterior, mpmath criterion) with the cases' own boxes, scales, starts
+and options, counting the records whose Armijo inequality lies inside the band the GPU test may skip,
+8 2^-53 (|a| + |a_y| + c1 sum |g_k delta_k|).  The GPU test allows 2 % per shape.  Cov_se_iso shapes only: the evaluator does
+not cover the projection case (m = 20, 5 -> 2), which is reported as not checked.
+    usage (repo root, no GPU): python3 tools/refine_precheck.py [--out profiles/refine_precheck.txt]
+"""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tests import refine_cases as RC  # noqa: E402
+from tests import refine_ref as RR  # noqa: E402
+from tests import test_gpu_refine as T  # noqa: E402
+
+EPS = 2.0 ** -53
+out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
+shapes = [(1, m, d, None, ns) for m, d, ns in T.ROUTE_1] + [(2, m, d, D, ns) for m, d, D, ns in T.ROUTE_2]
+lines = ["# tools/refine_precheck.py: tests/refine_ref.py over the 80-bit evaluator on the trace cases of tests/test_gpu_refine.py;",
+         "# ties: records whose Armijo inequality lies inside the band the GPU test may skip (cap: 2 % per shape)",
+         "%-6s %4s %3s %-22s %8s %6s %7s" % ("route", "m", "d", "ns", "records", "ties", "share")]
+for route, m, d, D, ns_list in shapes:
+    if D:
+        lines.append("%-6d %4d %3d %-22s not checked (projection: outside the CPU evaluator)" % (route, m, d, ns_list))
+        continue
+    X, y, Z, args = RC.data(m, d)
+    post = RC.posterior(X, y, Z, args)
+    best = (float(np.min(y)), float(np.max(y)))
+    lo, hi = np.full(d, 0.05), np.linspace(0.9, 1.1, d)
+    records = ties = 0
+    for ns in ns_list:
+        for ki, (kind, maximise, extra) in enumerate(T.KINDS):
+            kw = {k: v for k, v in T._kw(kind, maximise, best, extra).items() if k != "predictive"}
+            scale = None if ki % 2 == 0 else np.linspace(0.5, 1.5, d)
+            S = T._starts(d, ns, lo, hi, 7 * ns + ki)
+            f = RC.evaluator(post, kind, **kw)
+            for i in range(ns):
+                r = RR.refine(f, S[:, i], lo, hi, scale, **T.OPTS)
+                x, g, a = (np.array(r["trace"][0][0]), np.array(r["trace"][0][1]), r["trace"][0][2])
+                for yy, gy, ay, alpha, acc in r["trace"][1:]:
+                    delta = np.array(yy) - x
+                    records += 1
+                    band = 8 * EPS * (abs(a) + abs(ay) + T.OPTS["c1"] * float(np.sum(np.abs(g * delta))))
+                    ties += abs(ay - (a + T.OPTS["c1"] * float(np.dot(g, delta)))) < band
+                    if acc:
+                        x, g, a = np.array(yy), np.array(gy), ay
+    lines.append("%-6d %4d %3d %-22s %8d %6d %6.2f%%" % (route, m, d, ns_list, records, ties, 100.0 * ties / max(records, 1)))
+    print(lines[-1], flush=True)
+text = "\n".join(lines) + "\n"
+if out_path:
+    with open(out_path, "w") as fh:
+        fh.write(text)
