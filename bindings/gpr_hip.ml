@@ -62,6 +62,10 @@ external acquire_refine : problem -> vec -> vec -> mat -> mat -> mat -> vec -> u
 (* posterior sample paths (gprhip_sample_paths): z (m x ns normal draws) -> points -> eps (nt x ns, or None: the path part
    alone) -> samples (nt x ns) *)
 external sample_paths : problem -> mat -> mat -> mat option -> mat -> unit = "gprhip_ml_sample_paths"
+(* the draws refined inside a box (gprhip_sample_paths_refine): z -> maximise -> options (as acquire_refine) -> box (D x 2) ->
+   starts (D x ns) -> draw_of (ns, the draw each start climbs) -> x_out (D x ns) -> values (ns: the objective s f_j at x_out) *)
+external sample_paths_refine : problem -> mat -> bool -> vec -> mat -> mat -> vec -> mat -> vec -> unit
+  = "gprhip_ml_sample_paths_refine_bc" "gprhip_ml_sample_paths_refine"
 external train_stats : problem -> vec option -> vec -> unit = "gprhip_ml_train_stats"
 external covariances : problem -> mat -> int -> bool -> mat -> unit = "gprhip_ml_covariances"
 external cov_samples : problem -> mat -> float -> float -> vec -> mat -> mat -> unit

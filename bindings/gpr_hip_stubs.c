@@ -16,6 +16,7 @@
 #include <caml/memory.h>
 #include <caml/mlvalues.h>
 #include <caml/threads.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "gprhip.h"
@@ -263,6 +264,57 @@ CAMLprim value gprhip_ml_sample_paths(value prob, value z, value points, value e
   caml_acquire_runtime_system();
   check(status);
   CAMLreturn(Val_unit);
+}
+
+/* external sample_paths_refine : problem -> z:mat -> bool -> vec -> mat -> mat -> vec -> mat -> vec -> unit
+ *   refines drawn sample paths inside a box (gprhip_sample_paths_refine): z (m x nd) as sample_paths, maximise, options
+ *   [| max_evals; step0; c1; shrink; grow; xtol |], box D x 2 (lower, upper), starts D x ns, draw_of ns (the draw of each
+ *   start, as floats), x_out D x ns, values ns (the objective s f_j at x_out) */
+CAMLprim value gprhip_ml_sample_paths_refine(value prob, value z, value maximise, value options, value box, value starts,
+                                             value draw_of, value x_out, value values) {
+  CAMLparam5(prob, z, maximise, options, box);
+  CAMLxparam4(starts, draw_of, x_out, values);
+  struct caml_ba_array* ba = Caml_ba_array_val(starts);
+  struct caml_ba_array* bz = Caml_ba_array_val(z);
+  gprhip_problem* p = Problem_val(prob);
+  const double* x = (const double*)ba->data;
+  const double* zz = (const double*)bz->data;
+  int64_t ld = ba->dim[0], ns = ba->dim[1], ldz = bz->dim[0], i;
+  int nd = (int)bz->dim[1];
+  const double* o = (const double*)Caml_ba_data_val(options);
+  const double* b = (const double*)Caml_ba_data_val(box);
+  const double* dr = (const double*)Caml_ba_data_val(draw_of);
+  double* xo = (double*)Caml_ba_data_val(x_out);
+  double* a = (double*)Caml_ba_data_val(values);
+  gprhip_refine_options opt;
+  int* draws;
+  int status;
+  if (Caml_ba_array_val(options)->dim[0] != 6) caml_invalid_argument("Gpr_hip.sample_paths_refine: six options");
+  if (Caml_ba_array_val(box)->dim[0] != ld || Caml_ba_array_val(box)->dim[1] != 2)
+    caml_invalid_argument("Gpr_hip.sample_paths_refine: the box is D x 2");
+  if (Caml_ba_array_val(x_out)->dim[0] != ld || Caml_ba_array_val(x_out)->dim[1] != ns ||
+      Caml_ba_array_val(values)->dim[0] != ns || Caml_ba_array_val(draw_of)->dim[0] != ns)
+    caml_invalid_argument("Gpr_hip.sample_paths_refine: x_out is D x ns, values and draw_of ns");
+  opt.max_evals = (int)o[0];
+  opt.step0 = o[1];
+  opt.c1 = o[2];
+  opt.shrink = o[3];
+  opt.grow = o[4];
+  opt.xtol = o[5];
+  draws = (int*)malloc((size_t)(ns > 0 ? ns : 1) * sizeof(int));
+  if (!draws) caml_raise_out_of_memory();
+  for (i = 0; i < ns; ++i) draws[i] = (int)dr[i];
+  caml_release_runtime_system();
+  status = gprhip_sample_paths_refine(p, zz, ldz, nd, Bool_val(maximise), &opt, b, b + ld, NULL, x, ld, ns, draws, xo, ld, a, NULL,
+                                      ld, NULL, NULL, NULL, NULL, 0);
+  caml_acquire_runtime_system();
+  free(draws);
+  check(status);
+  CAMLreturn(Val_unit);
+}
+CAMLprim value gprhip_ml_sample_paths_refine_bc(value* argv, int argn) {
+  (void)argn;
+  return gprhip_ml_sample_paths_refine(argv[0], argv[1], argv[2], argv[3], argv[4], argv[5], argv[6], argv[7], argv[8]);
 }
 
 /* external train_stats : problem -> means:vec option -> sums:vec -> unit      sums = [sse; sum|e|; max|e|; sum y^2] */

@@ -155,6 +155,9 @@ SIGNATURES = {
                                         _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int]),
     "gprhip_sample_paths": (C.c_int, [_vp, _dp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int, _vp, C.c_int64,
                                       C.c_int, C.c_int, C.POINTER(C.c_int64), _dp, _dp, C.c_int]),
+    "gprhip_sample_paths_refine": (C.c_int, [_vp, _dp, C.c_int64, C.c_int, C.c_int, C.POINTER(RefineOptions), _dp, _dp, _dp, _vp,
+                                             C.c_int64, C.c_int64, C.POINTER(C.c_int), _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp,
+                                             _vp, _vp, C.c_int]),
     "gprhip_predict_targets": (C.c_int, [_vp, _dp, C.c_int64, C.c_int64, _dp]),
     "gprhip_train_stats": (C.c_int, [_vp, _dp, _dp]),
     "gprhip_covariances": (C.c_int, [_vp, _dp, C.c_int64, C.c_int64, C.c_int, C.c_int, _dp]),

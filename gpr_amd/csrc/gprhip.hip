@@ -2538,6 +2538,121 @@ void do_sample_paths(gprhip_problem* p, const double* z, int64_t ldz, int ns, co
   if (p->timer.on) tcollect(p);
 }
 
+// gprhip_sample_paths_refine: the rule of refine_step.h on drawn sample paths (path_refine.hip).  The weights A are formed
+// once per call as gprhip_sample_paths forms them; start i climbs s f_{draw_of[i]}.
+//   * no projection: one persistent kernel at every m -- an evaluation costs O(m d) per start, the loop runs on the device;
+//   * with a projection: the loop runs here as route 2 of gprhip_acquire_refine does -- the trial points are projected, one
+//     launch of the same evaluator, the back-projection of its gradient, refine_step_kernel, one integer back.
+// The caller has checked the arguments and the model state; hs: the starts on the host, [ns][D], finite.  pg_m is neither
+// needed nor formed.
+void do_sample_paths_refine(gprhip_problem* p, const double* z, int64_t ldz, int nd, int maximise,
+                            const gprhip_refine_options* opt, const double* lower, const double* upper, const double* scale,
+                            std::vector<double>& hs, int64_t ns, const int* draw_of, double* x_out, int64_t ldx, double* values,
+                            double* dvalues, int64_t ldg, int* evals, int* accepted, int* status, double* trace, int on_device) {
+  const char* const fn = "gprhip_sample_paths_refine";
+  GPR_HIP(hipSetDevice(p->device));
+  hipStream_t s = p->stream;
+  const int D = p->D, d = p->d, m = p->m, mp = p->mp;
+  const bool proj = p->has_proj();
+  const int64_t rec = 2 * D + 3, nsD = ns * D;
+  const int64_t trace_len = (trace && !on_device) ? ns * opt->max_evals * rec : 0;
+  const int64_t len = 3 * D + 4 * nsD + 3 * ns + (4 * ns + 1) / 2 + trace_len;
+  const bool grow = p->rf_len < len;
+  int64_t extra = grow ? len * 8 : 0;
+  if (!p->sp_coef) extra += 2 * (int64_t)mp * SP_MAX_DRAWS * 8;
+  const PgPlan plan = pg_prepare(p, fn, ns, false, false, true, extra);
+  if (proj && plan.chunk < ns) {  // (a chunk holds every count of starts the call accepts)
+    set_error(std::string(fn) + ": the starts do not fit one chunk of test points");
+    throw HipFail{ST_BAD_ARG};
+  }
+  if (grow) {
+    GPR_HIP(hipStreamSynchronize(s));
+    release_buf(p, p->rf_buf);
+    p->rf_len = 0;
+    p->rf_buf = p->alloc<double>(len);
+    p->rf_len = len;
+  }
+  if (proj && !p->rf_active) GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->rf_active), sizeof(int), hipHostMallocDefault));
+  if (!p->sp_zhost)
+    GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->sp_zhost), (size_t)mp * SP_MAX_DRAWS * sizeof(double),
+                          hipHostMallocPortable | hipHostMallocMapped));
+  if (!p->sp_coef) p->sp_coef = p->alloc<double>(2 * (int64_t)mp * SP_MAX_DRAWS);
+  double* const bnd = p->rf_buf;
+  double *const Y = bnd + 3 * D, *const X = Y + nsD, *const G = X + nsD, *const GY = G + nsD;
+  double *const A = GY + nsD, *const AY = A + ns, *const AL = AY + ns;
+  int* const ints = reinterpret_cast<int*>(AL + ns);  // evals | accepted | status | draw_of
+  double* const trace_dev = trace ? (on_device ? trace : AL + ns + (4 * ns + 1) / 2) : nullptr;
+  GPR_HIP(hipMemcpyAsync(bnd, lower, (size_t)D * 8, hipMemcpyHostToDevice, s));
+  GPR_HIP(hipMemcpyAsync(bnd + D, upper, (size_t)D * 8, hipMemcpyHostToDevice, s));
+  if (scale) GPR_HIP(hipMemcpyAsync(bnd + 2 * D, scale, (size_t)D * 8, hipMemcpyHostToDevice, s));
+  GPR_HIP(hipMemcpyAsync(ints + 3 * ns, draw_of, (size_t)ns * sizeof(int), hipMemcpyHostToDevice, s));
+  if (trace && !on_device)  // records that no evaluation writes keep what the caller's buffer holds
+    GPR_HIP(hipMemcpyAsync(trace_dev, trace, (size_t)trace_len * 8, hipMemcpyHostToDevice, s));
+  for (int64_t i = 0; i < nsD; ++i) hs[i] = refine_clip(hs[i], lower[i % D], upper[i % D]);
+  GPR_HIP(hipMemcpyAsync(Y, hs.data(), (size_t)nsD * 8, hipMemcpyHostToDevice, s));
+  // the weights, once per call: R~^-1 Z first, then U^-1 times it, plus t
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j < nd; ++j) p->sp_zhost[(int64_t)i * SP_MAX_DRAWS + j] = z[(int64_t)j * ldz + i];
+  double* const wA = p->sp_coef + (int64_t)mp * SP_MAX_DRAWS;
+  tstart(p, "sp_coeff");
+  launch_sp_weights(p->rinv, p->uinv, p->sp_zhost, p->tvec, m, mp, nd, p->sp_coef, wA, s);
+  tstop(p);
+  // the persistent kernel keeps its state in the caller's device buffers where there are some
+  const bool direct = !proj && on_device;
+  RefineStepArgs st;
+  st.ns = (int)ns; st.D = D; st.first = 1; st.lower = bnd; st.upper = bnd + D; st.scale = scale ? bnd + 2 * D : nullptr;
+  st.o.max_evals = opt->max_evals; st.o.step0 = opt->step0; st.o.c1 = opt->c1; st.o.shrink = opt->shrink;
+  st.o.grow = opt->grow; st.o.xtol = opt->xtol;
+  st.x = (direct && x_out) ? x_out : X; st.g = (direct && dvalues) ? dvalues : G; st.y = Y; st.gy = GY; st.ay = AY;
+  st.a = (direct && values) ? values : A; st.alpha = AL;
+  st.evals = (direct && evals) ? evals : ints; st.accepted = (direct && accepted) ? accepted : ints + ns;
+  st.status = (direct && status) ? status : ints + 2 * ns;
+  st.trace = trace_dev; st.active = p->rf_active;
+  PathEvalArgs e;
+  e.pts = Y; e.Z = p->Z; e.shift = p->zshift; e.W = wA; e.draw_of = ints + 3 * ns; e.status = st.status;
+  e.rows = (int)ns; e.m = m; e.d = d; e.nd = nd; e.log_sf2 = p->cp.log_sf2; e.inv_ell2_05 = p->cp.inv_ell2_05;
+  e.sign = maximise ? 1.0 : -1.0; e.val = AY; e.grad = GY; e.ldg = D;
+  if (!proj) {
+    tstart(p, "prf_kernel");
+    launch_path_refine(e, st, s);
+    tstop(p);
+  } else {
+    e.grad = plan.stage_p[0]; e.ldg = d;
+    for (int ev = 0; ev < st.o.max_evals; ++ev) {
+      st.first = ev == 0;
+      e.status = ev == 0 ? nullptr : st.status;
+      walk_chunks(p, plan.chunk, Y, D, ns, 1, [&](int64_t, int rows, int, const double*, const double* pts) {
+        tstart(p, "prf_eval");
+        e.pts = pts;
+        launch_path_eval(e, s);
+        launch_input_grad_project(e.grad, rows, d, D, p->tproj, GY, D, s);
+        tstop(p);
+        tstart(p, "rf_step");
+        launch_refine_step(st, s);
+        tstop(p);
+      });
+      if (*static_cast<volatile int*>(p->rf_active) == 0) break;
+    }
+  }
+  {  // from the library's buffers to the caller's
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const double* const mats[2] = {st.x, st.g};
+    double* const dst[2] = {x_out, dvalues};
+    const int64_t lds[2] = {ldx, ldg};
+    for (int j = 0; j < 2; ++j)
+      if (dst[j] && dst[j] != mats[j])
+        GPR_HIP(hipMemcpy2DAsync(dst[j], (size_t)lds[j] * 8, mats[j], (size_t)D * 8, (size_t)D * 8, (size_t)ns, kind, s));
+    if (values && values != st.a) GPR_HIP(hipMemcpyAsync(values, st.a, (size_t)ns * 8, kind, s));
+    int* const idst[3] = {evals, accepted, status};
+    const int* const isrc[3] = {st.evals, st.accepted, st.status};
+    for (int j = 0; j < 3; ++j)
+      if (idst[j] && idst[j] != isrc[j]) GPR_HIP(hipMemcpyAsync(idst[j], isrc[j], (size_t)ns * sizeof(int), kind, s));
+    if (trace && !on_device) GPR_HIP(hipMemcpyAsync(trace, trace_dev, (size_t)trace_len * 8, hipMemcpyDeviceToHost, s));
+  }
+  GPR_HIP(hipStreamSynchronize(s));
+  if (p->timer.on) tcollect(p);
+}
+
 // Temporary device memory of one posterior call (sizes depend on the number of test points).
 struct DevBuf {
   std::vector<void*> ptrs;
@@ -3817,6 +3932,59 @@ int gprhip_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const doubl
   }, p);
 }
 
+// what gprhip_acquire_refine and gprhip_sample_paths_refine refuse of the options, the number of starts and the outputs ...
+void check_refine_options(const char* fn, const gprhip_refine_options* opt, int64_t ns, bool any_output) {
+  auto refuse = [&](const std::string& why) {
+    set_error(std::string(fn) + ": " + why);
+    throw HipFail{ST_BAD_ARG};
+  };
+  if (!opt) refuse("invalid arguments (opt is NULL)");
+  if (opt->max_evals < 1 || opt->max_evals > GPRHIP_REFINE_MAX_EVALS) refuse("max_evals must lie in 1 .. GPRHIP_REFINE_MAX_EVALS (1000)");
+  if (!(opt->step0 > 0.0 && opt->step0 <= 1.0)) refuse("step0 must lie in (0, 1]");
+  if (!(opt->c1 >= 0.0 && opt->c1 < 1.0)) refuse("c1 must lie in [0, 1)");
+  if (!(opt->shrink > 0.0 && opt->shrink < 1.0)) refuse("shrink must lie in (0, 1)");
+  if (!(opt->grow >= 1.0) || !std::isfinite(opt->grow)) refuse("grow must be finite and at least 1");
+  if (!(opt->xtol >= 0.0) || !std::isfinite(opt->xtol)) refuse("xtol must be finite and not negative");
+  if (ns < 1 || ns > GPRHIP_REFINE_MAX_STARTS) refuse("ns must lie in 1 .. GPRHIP_REFINE_MAX_STARTS (4096)");
+  if (!any_output) refuse("nothing is requested (all outputs are NULL)");
+}
+
+// ... and of the leading dimensions, the box and the scale (p, lower and upper are not NULL)
+void check_refine_box(const char* fn, const gprhip_problem* p, const double* lower, const double* upper, const double* scale,
+                      int64_t ld, const double* x_out, int64_t ldx, const double* dvalues, int64_t ldg, int on_device) {
+  auto refuse = [&](const std::string& why) {
+    set_error(std::string(fn) + ": " + why);
+    throw HipFail{ST_BAD_ARG};
+  };
+  const int D = p->D;
+  if (on_device ? ld != D : ld < D) refuse("bad ld (need ld == D for device buffers, ld >= D for host buffers)");
+  if (x_out && (on_device ? ldx != D : ldx < D)) refuse("bad ldx (need ldx == D for device buffers, ldx >= D for host buffers)");
+  if (dvalues && (on_device ? ldg != D : ldg < D)) refuse("bad ldg (need ldg == D for device buffers, ldg >= D for host buffers)");
+  for (int k = 0; k < D; ++k) {
+    if (!std::isfinite(lower[k]) || !std::isfinite(upper[k]) || !(lower[k] < upper[k])) refuse("lower and upper must be finite with lower < upper");
+    if (scale && (!(scale[k] > 0.0) || !std::isfinite(scale[k]))) refuse("scale must be positive and finite");
+  }
+}
+
+// the starts on the host, [ns][D]; a non-finite one is refused.  Called after the model-state checks: the starts of a device
+// call are read back here, and a refused call enqueues nothing
+std::vector<double> refine_starts(const char* fn, gprhip_problem* p, const double* starts, int64_t ld, int64_t ns, int on_device) {
+  const int D = p->D;
+  std::vector<double> hs((size_t)ns * D);
+  if (on_device) {
+    GPR_HIP(hipSetDevice(p->device));
+    GPR_HIP(hipMemcpy(hs.data(), starts, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
+  } else {
+    for (int64_t i = 0; i < ns; ++i) std::copy(starts + i * ld, starts + i * ld + D, hs.begin() + i * D);
+  }
+  for (double v : hs)
+    if (!std::isfinite(v)) {
+      set_error(std::string(fn) + ": the starts must be finite");
+      throw HipFail{ST_BAD_ARG};
+    }
+  return hs;
+}
+
 int gprhip_acquire_refine(gprhip_problem* p, const gprhip_acquisition* acq, const gprhip_refine_options* opt, const double* lower,
                           const double* upper, const double* scale, const double* starts, int64_t ld, int64_t ns, double* x_out,
                           int64_t ldx, double* values, double* dvalues, int64_t ldg, int* evals, int* accepted, int* status,
@@ -3828,40 +3996,44 @@ int gprhip_acquire_refine(gprhip_problem* p, const gprhip_acquisition* acq, cons
       throw HipFail{ST_BAD_ARG};
     };
     check_acquisition(fn, acq);
-    if (!opt) refuse("invalid arguments (opt is NULL)");
-    if (opt->max_evals < 1 || opt->max_evals > GPRHIP_REFINE_MAX_EVALS) refuse("max_evals must lie in 1 .. GPRHIP_REFINE_MAX_EVALS (1000)");
-    if (!(opt->step0 > 0.0 && opt->step0 <= 1.0)) refuse("step0 must lie in (0, 1]");
-    if (!(opt->c1 >= 0.0 && opt->c1 < 1.0)) refuse("c1 must lie in [0, 1)");
-    if (!(opt->shrink > 0.0 && opt->shrink < 1.0)) refuse("shrink must lie in (0, 1)");
-    if (!(opt->grow >= 1.0) || !std::isfinite(opt->grow)) refuse("grow must be finite and at least 1");
-    if (!(opt->xtol >= 0.0) || !std::isfinite(opt->xtol)) refuse("xtol must be finite and not negative");
-    if (ns < 1 || ns > GPRHIP_REFINE_MAX_STARTS) refuse("ns must lie in 1 .. GPRHIP_REFINE_MAX_STARTS (4096)");
-    if (!x_out && !values && !dvalues && !evals && !accepted && !status && !trace) refuse("nothing is requested (all outputs are NULL)");
+    check_refine_options(fn, opt, ns, x_out || values || dvalues || evals || accepted || status || trace);
     if (!p || !starts || !lower || !upper) refuse("invalid arguments");
     if (p->f32) refuse("the prediction gradient is evaluated in fp64 only (GPRHIP_F32_BULK problem)");
     if (p->d > 64) refuse("at most 64 point dimensions on the kernel side (d)");
-    const int D = p->D;
-    if (on_device ? ld != D : ld < D) refuse("bad ld (need ld == D for device buffers, ld >= D for host buffers)");
-    if (x_out && (on_device ? ldx != D : ldx < D)) refuse("bad ldx (need ldx == D for device buffers, ldx >= D for host buffers)");
-    if (dvalues && (on_device ? ldg != D : ldg < D)) refuse("bad ldg (need ldg == D for device buffers, ldg >= D for host buffers)");
-    for (int k = 0; k < D; ++k) {
-      if (!std::isfinite(lower[k]) || !std::isfinite(upper[k]) || !(lower[k] < upper[k])) refuse("lower and upper must be finite with lower < upper");
-      if (scale && (!(scale[k] > 0.0) || !std::isfinite(scale[k]))) refuse("scale must be positive and finite");
-    }
+    check_refine_box(fn, p, lower, upper, scale, ld, x_out, ldx, dvalues, ldg, on_device);
     // the model state before the starts are read back from the device: a refused call enqueues nothing
     need_posterior_state(p, fn, "predict from", true, !(acq->kind == GPRHIP_ACQ_BOUND && acq->kappa == 0.0), true,
                          "means and their gradients are available after the next gprhip_eval");
-    std::vector<double> hs((size_t)ns * D);
-    if (on_device) {
-      GPR_HIP(hipSetDevice(p->device));
-      GPR_HIP(hipMemcpy(hs.data(), starts, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
-    } else {
-      for (int64_t i = 0; i < ns; ++i) std::copy(starts + i * ld, starts + i * ld + D, hs.begin() + i * D);
-    }
-    for (double v : hs)
-      if (!std::isfinite(v)) refuse("the starts must be finite");
+    std::vector<double> hs = refine_starts(fn, p, starts, ld, ns, on_device);
     do_acquire_refine(p, acq, opt, lower, upper, scale, starts, hs, ns, x_out, ldx, values, dvalues, ldg, evals, accepted, status,
                       trace, on_device);
+  }, p);
+}
+
+int gprhip_sample_paths_refine(gprhip_problem* p, const double* z, int64_t ldz, int nd, int maximise,
+                               const gprhip_refine_options* opt, const double* lower, const double* upper, const double* scale,
+                               const double* starts, int64_t ld, int64_t ns, const int* draw_of, double* x_out, int64_t ldx,
+                               double* values, double* dvalues, int64_t ldg, int* evals, int* accepted, int* status,
+                               double* trace, int on_device) {
+  return guarded([&] {
+    const char* const fn = "gprhip_sample_paths_refine";
+    auto refuse = [&](const std::string& why) {
+      set_error(std::string(fn) + ": " + why);
+      throw HipFail{ST_BAD_ARG};
+    };
+    if (nd < 1 || nd > GPRHIP_MAX_DRAWS) refuse("nd must lie in 1 .. GPRHIP_MAX_DRAWS (64)");
+    check_refine_options(fn, opt, ns, x_out || values || dvalues || evals || accepted || status || trace);
+    if (!p || !z || !starts || !draw_of || !lower || !upper) refuse("invalid arguments");
+    if (p->f32) refuse("sample paths are evaluated in fp64 only (GPRHIP_F32_BULK problem)");
+    if (p->d > 64) refuse("at most 64 point dimensions on the kernel side (d)");
+    if (ldz < p->m) refuse("bad ldz (need ldz >= m)");
+    check_refine_box(fn, p, lower, upper, scale, ld, x_out, ldx, dvalues, ldg, on_device);
+    for (int64_t i = 0; i < ns; ++i)
+      if (draw_of[i] < 0 || draw_of[i] >= nd) refuse("draw_of must lie in 0 .. nd - 1");
+    need_posterior_state(p, fn, "draw from", true, true, true, "draws are available after the next gprhip_eval");
+    std::vector<double> hs = refine_starts(fn, p, starts, ld, ns, on_device);
+    do_sample_paths_refine(p, z, ldz, nd, maximise, opt, lower, upper, scale, hs, ns, draw_of, x_out, ldx, values, dvalues, ldg,
+                           evals, accepted, status, trace, on_device);
   }, p);
 }
 

@@ -413,6 +413,27 @@ struct PathGradAtArgs {
 };
 void launch_path_grad_at(const PathGradAtArgs& a, hipStream_t s);
 
+// ---- gprhip_sample_paths_refine (path_refine.hip): the rule of refine_step.h on drawn sample paths.  Row r climbs
+// o(x) = sign sum_c k(x, z_c) W[c][draw_of[r]]
+struct PathEvalArgs {
+  const double* pts;       // [rows][d]  trial points (their projections where the model has one)
+  const double *Z, *shift; // [mp][d], [d]
+  const double* W;         // [mp][SP_MAX_DRAWS] weights of launch_sp_weights
+  const int* draw_of;      // [rows] (device), entries in 0 .. nd - 1
+  const int* status;       // [rows] or null: rows whose status is not REFINE_ACTIVE are skipped, nothing is stored for them
+  int rows, m, d, nd;      // d <= 64, 1 <= nd <= SP_MAX_DRAWS
+  double log_sf2, inv_ell2_05, sign;
+  double* val;             // out [rows]: o
+  double* grad;            // out [rows][ldg]: do/dp (d entries per row)
+  int64_t ldg;
+};
+// one evaluation at all rows (the library-side loop of models with a projection)
+void launch_path_eval(const PathEvalArgs& e, hipStream_t s);
+// One persistent kernel, 64 starts per workgroup, any m: the evaluation loop runs inside it on the arrays of st, which the
+// evaluator reads and writes (e.pts = st.y holding the clipped starts, e.val = st.ay, e.grad = st.gy, e.status = st.status,
+// e.ldg = e.d = st.D, e.rows = st.ns; st.first and st.active are not used).  No projection.
+void launch_path_refine(const PathEvalArgs& e, const RefineStepArgs& st, hipStream_t s);
+
 // ---- m x m finalisation (finalize.hip)
 // dst (upper tiles) = base + sum_z slices[z]; the diagonal tiles sum the first nslices_diag slices only (0 = nslices;
 // gemm_syrk_diag_slices for the result of a SYRK-shaped engine launch)

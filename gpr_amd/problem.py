@@ -400,6 +400,62 @@ class Problem:
                                                    ptrs["accepted"], ptrs["status"], ptrs["trace"], on_device))
         return out
 
+    def sample_paths_refine(self, starts, z, draw_of, *, lower, upper, maximise=True, scale=None, max_evals=50, step0=0.1,
+                            c1=1e-4, shrink=0.5, grow=2.0, xtol=1e-8,
+                            want=("x", "values", "dvalues", "evals", "accepted", "status"), out_device_ptrs=None, ns=None):
+        """Refines drawn sample paths on the device (gprhip_sample_paths_refine): the rule of `acquire_refine` on the draws of
+        `sample_paths`.  z: m x nd standard normal draws (host, 1 <= nd <= 64), the same z as in `sample_paths` gives the same
+        functions; draw_of: ns integers in 0 .. nd - 1, the draw that each column of `starts` (D x ns) climbs.  The objective
+        is s f_j with s = +1 if maximise else -1: values, dvalues and the trace hold the objective and its gradient, not the
+        unsigned path.  Box, scale, the rule's constants, `want`, the outputs and out_device_ptrs / ns as `acquire_refine`
+        (z and draw_of stay host arrays)."""
+        want = tuple(want)
+        unknown = [w for w in want if w not in self.REFINE_OUTPUTS]
+        if unknown:
+            raise ValueError("sample_paths_refine: unknown outputs %s" % unknown)
+        z = np.asfortranarray(z, dtype=np.float64)
+        if z.ndim != 2 or z.shape[0] != self.m:
+            raise ValueError("sample_paths_refine: expected z of shape (%d, nd)" % self.m)
+        nd = z.shape[1]
+        opt = _lib.RefineOptions(int(max_evals), float(step0), float(c1), float(shrink), float(grow), float(xtol))
+        box = [np.ascontiguousarray(b, dtype=np.float64) for b in (lower, upper)]
+        if scale is not None:
+            box.append(np.ascontiguousarray(scale, dtype=np.float64))
+        if any(b.shape != (self.D,) for b in box):
+            raise ValueError("sample_paths_refine: lower, upper and scale take %d entries each" % self.D)
+        bptr = [_f64_ptr(b) for b in box] + ([None] if scale is None else [])
+        null = C.c_void_p(None)
+        out = {}
+        if out_device_ptrs is not None:
+            if ns is None:
+                raise ValueError("sample_paths_refine: device buffers need ns")
+            ptrs = {w: (C.c_void_p(int(out_device_ptrs[w])) if w in want else null) for w in self.REFINE_OUTPUTS}
+            st_ptr, on_device, ns = C.c_void_p(int(starts)), 1, int(ns)
+        else:
+            xs = np.asfortranarray(starts, dtype=np.float64)
+            if xs.ndim != 2 or xs.shape[0] != self.D:
+                raise ValueError("sample_paths_refine: expected starts of shape (%d, ns)" % self.D)
+            ns = xs.shape[1]
+            for w in want:
+                if w in ("x", "dvalues"):
+                    out[w] = np.full((self.D, ns), np.nan, dtype=np.float64, order="F")
+                elif w == "values":
+                    out[w] = np.full(ns, np.nan, dtype=np.float64)
+                elif w == "trace":
+                    out[w] = np.full((ns, int(max_evals), 2 * self.D + 3), np.nan, dtype=np.float64)
+                else:
+                    out[w] = np.full(ns, -1, dtype=np.int32)
+            ptrs = {w: (C.c_void_p(out[w].ctypes.data) if w in out else null) for w in self.REFINE_OUTPUTS}
+            st_ptr, on_device = C.c_void_p(xs.ctypes.data), 0
+        dr = np.ascontiguousarray(draw_of, dtype=np.int32)
+        if dr.shape != (ns,):
+            raise ValueError("sample_paths_refine: draw_of takes %d entries" % ns)
+        _lib.check(self._lib.gprhip_sample_paths_refine(self._handle(), _f64_ptr(z), self.m, nd, int(bool(maximise)), C.byref(opt),
+                                                        *bptr, st_ptr, self.D, ns, dr.ctypes.data_as(C.POINTER(C.c_int)),
+                                                        ptrs["x"], self.D, ptrs["values"], ptrs["dvalues"], self.D,
+                                                        ptrs["evals"], ptrs["accepted"], ptrs["status"], ptrs["trace"], on_device))
+        return out
+
     def sample_paths(self, test_inputs, z, eps=None, predictive=False, maximise=True, top_k=0, want_samples=True,
                      out_device_ptrs=None, nt=None):
         """Posterior sample paths at test points (gprhip_sample_paths).  z: m x ns standard normal draws (host, 1 <= ns <= 64);

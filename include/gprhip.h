@@ -438,8 +438,8 @@ int gprhip_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const doubl
  * bad ld / ldx / ldg.  State and limits: as gprhip_acquire (GPRHIP_ESTATE under the same conditions; BOUND with kappa == 0 runs
  * the mean part alone and needs no factors).  New buffers are checked against the free device memory first (GPRHIP_EOOM).  A
  * refused call enqueues nothing; the call never changes the predictor state.
- * Limits: no optimiser other than this one (no L-BFGS, no q-batch criteria); drawn sample paths are not refined; fp64 problems,
- * one device, no multiscales.
+ * Limits: no optimiser other than this one (no L-BFGS, no q-batch criteria); drawn sample paths are refined by
+ * gprhip_sample_paths_refine, not here; fp64 problems, one device, no multiscales.
  * Stage timers: "rf_small" (the persistent kernel); on the other route those of gprhip_acquire per evaluation and "rf_step". */
 enum { GPRHIP_REFINE_ST_CONVERGED = 0, GPRHIP_REFINE_ST_MAX_EVALS = 1, GPRHIP_REFINE_ST_NAN = 2 };
 #define GPRHIP_REFINE_MAX_EVALS 1000
@@ -491,6 +491,44 @@ int gprhip_acquire_refine(gprhip_problem* p, const gprhip_acquisition* acq, cons
 int gprhip_sample_paths(gprhip_problem* p, const double* z, int64_t ldz, int ns, const double* test_inputs, int64_t ld,
                         int64_t nt, const double* eps, int64_t lde, int predictive, double* samples, int64_t lds, int maximise,
                         int top_k, int64_t* top_index, double* top_values, double* top_dvalues, int on_device);
+
+/* Refines drawn sample paths on the device: the maximiser (maximise = 0: minimiser) of each draw f_j, what Thompson sampling
+ * wants after gprhip_sample_paths has named the best grid points of every draw (an extension beyond the reference's
+ * implemented surface).
+ *   z: HOST always, Fortran m x nd (ldz >= m), 1 <= nd <= GPRHIP_MAX_DRAWS.  Column j fixes draw j exactly as in
+ *      gprhip_sample_paths: a_j = t + U^-1 (R~^-1 z_j), f_j(x) = sum_c k(x, z_c) a_cj.  The same z gives the same function.
+ *   draw_of: HOST always, ns ints in 0 .. nd - 1: the draw that each start climbs.  Any assignment is allowed; the usual one
+ *      is the top_k winners of draw j as the starts of draw j.
+ * The objective of start i is o(x) = s f_{draw_of[i]}(x) with s = +1 if maximise, else -1, its gradient s grad f: "larger is
+ * better", as with the criteria.  values, dvalues and the trace hold the OBJECTIVE and its gradient -- the numbers the rule
+ * sees --, not the unsigned path: with maximise = 0 they are -f and -grad f.
+ * The rule (steps 1 - 4), gprhip_refine_options, the status codes, lower / upper / scale (HOST always, D doubles each; scale
+ * == NULL means all ones), every output and its layout in either mode, on_device, GPRHIP_REFINE_MAX_STARTS and
+ * GPRHIP_REFINE_MAX_EVALS are those of gprhip_acquire_refine, word for word -- the trace is [ns][max_evals][2 D + 3] doubles,
+ * evaluation j of a start writes record j = (y, g_y, a_y, alpha, accepted as 0 / 1), record 0 is the clipped start with
+ * alpha = 0 and accepted = 1, and records after the last evaluation are left untouched.
+ * Two routes, one rule, one evaluator.  A draw has m weights, so an evaluation with its gradient costs O(m d) per start: without
+ * a projection ONE persistent kernel runs the loop on the device at every m (64 starts per workgroup; the panels of Z - s and
+ * of the weights are staged again for every evaluation).  With a projection the loop runs in the library on device buffers:
+ * the trial points are projected, one launch of the same evaluator, the back-projection of its gradient, a step kernel, and
+ * one integer (the number of starts that go on) comes back per evaluation.  A start's result does not depend on the other
+ * starts, nor on their draws; it depends on nd only through the weights (gprhip_sample_paths' weight kernel splits its sums
+ * by the number of draws).  No atomics: two runs give the same bits.
+ * GPRHIP_EBADARG: what gprhip_acquire_refine refuses of the options, the box, scale, the starts, ns, the outputs and ld / ldx /
+ * ldg; nd outside 1 .. GPRHIP_MAX_DRAWS; a draw_of entry outside 0 .. nd - 1; bad ldz; an fp32-bulk problem, a model state with
+ * multiscales, more than 64 point dimensions on the kernel side.  GPRHIP_ESTATE: as gprhip_sample_paths.  New buffers are
+ * checked against the free device memory first (GPRHIP_EOOM).  A refused call enqueues nothing; the call never changes the
+ * predictor state; the matrix M of gprhip_predict_input_grad is neither needed nor formed.  A non-finite z is not refused: a
+ * NaN objective ends the start with GPRHIP_REFINE_ST_NAN, the starts of other draws are not touched by it.
+ * Limits: plain projected ascent (no L-BFGS); the path part only (no eps); fp64 problems, one device, no multiscales, d <= 64,
+ * nd <= 64, ns <= 4096.
+ * Stage timers: "sp_coeff" (the weights, once per call), "prf_kernel" (the persistent kernel); with a projection "prf_eval"
+ * (projection, evaluator and back-projection) and "rf_step" per evaluation. */
+int gprhip_sample_paths_refine(gprhip_problem* p, const double* z, int64_t ldz, int nd, int maximise,
+                               const gprhip_refine_options* opt, const double* lower, const double* upper, const double* scale,
+                               const double* starts, int64_t ld, int64_t ns, const int* draw_of, double* x_out, int64_t ldx,
+                               double* values, double* dvalues, int64_t ldg, int* evals, int* accepted, int* status,
+                               double* trace, int on_device);
 
 /* Training-set residual statistics with the model state left by the last evaluation (which must have had
  * targets): means[i] = K_nm[i,:] . coeffs over the resident training inputs (Trained.calc_means,

@@ -790,6 +790,26 @@ struct Make_deriv {
                                   b.top_dvalues.data(), 0));
         return b;
       }
+      // The starts (D x ns, in.points) refined on the draws of the sampler (gprhip_sample_paths_refine): start i climbs
+      // s f_{draw_of[i]} inside the box [lower, upper], s = +1 if maximise else -1; values / dvalues hold that objective and
+      // its gradient, not the unsigned path.  scale: nullptr for all ones.
+      static Refined_t refine(const Path_sampler_t& s, const Inputs_t& in, const std::vector<int>& draw_of,
+                              const gprhip_refine_options& opt, const Vec& lower, const Vec& upper, bool maximise = true,
+                              const Vec* scale = nullptr) {
+        Problem& p = problem_for(*s.trained, in, "Path_sampler.refine");
+        const size_t D = (size_t)in.points->rows, ns = (size_t)in.points->cols;
+        if (lower.size() != D || upper.size() != D || (scale && scale->size() != D))
+          throw std::invalid_argument("Path_sampler.refine: lower, upper and scale take D entries each");
+        if (draw_of.size() != ns) throw std::invalid_argument("Path_sampler.refine: draw_of takes one entry per start");
+        Refined_t r{Mat(in.points->rows, in.points->cols), Vec(ns), Mat(in.points->rows, in.points->cols), std::vector<int>(ns),
+                    std::vector<int>(ns), std::vector<int>(ns)};
+        check(gprhip_sample_paths_refine(p.get(), s.z.data(), s.z.rows, s.z.cols, maximise ? 1 : 0, &opt, lower.data(),
+                                         upper.data(), scale ? scale->data() : nullptr, in.points->data(), in.points->rows,
+                                         in.points->cols, draw_of.data(), r.x.data(), in.points->rows, r.values.data(),
+                                         r.dvalues.data(), in.points->rows, r.evals.data(), r.accepted.data(), r.status.data(),
+                                         nullptr, 0));
+        return r;
+      }
     };
     struct Covariances {  // FITC_covariances / FIC_covariances, :565-627
       template <class Owner>
