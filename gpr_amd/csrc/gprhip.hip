@@ -293,6 +293,7 @@ struct gprhip_problem {
   // weights A (2 [mp][64]); F / eps of one chunk ([64][sp_rows] each, made when a call needs them); the selection's
   // candidate lists and the winners' blocks [64][64 (D + 2)] with their pinned mirror
   double *sp_zhost = nullptr, *sp_coef = nullptr;
+  int sp_ns_last = 0;  // draws of the weights the second half of sp_coef holds; 0: none of the current model state
   double *sp_f = nullptr, *sp_eps = nullptr;
   int64_t sp_f_rows = 0, sp_eps_rows = 0;
   void* sp_scratch = nullptr;
@@ -1119,6 +1120,7 @@ void do_pass1(gprhip_problem* p, const gprhip_hypers* h, int want_grad, int64_t 
   p->x_last = nullptr;
   p->cond_km = -1.0;
   p->pg_m_valid = false;
+  p->sp_ns_last = 0;
   upload_hypers(p, h);
   p->want_grad = want_grad;
   p->n_total = n_total;
@@ -1759,6 +1761,7 @@ void batch_stage_lane(gprhip_batch* b, int j, const gprhip_hypers* h, int want_g
   l->x_last = nullptr;
   l->cond_km = -1.0;
   l->pg_m_valid = false;
+  l->sp_ns_last = 0;
   l->have_v = l->have_k = l->small_k_valid = false;
   stage_hypers(l, h);
   l->want_grad = want_grad;
@@ -2463,7 +2466,9 @@ void do_sample_paths(gprhip_problem* p, const double* z, int64_t ldz, int ns, co
   double* const w1 = p->sp_coef;
   double* const wA = p->sp_coef + (int64_t)mp * SP_MAX_DRAWS;
   tstart(p, "sp_coeff");
+  p->sp_ns_last = 0;
   launch_sp_weights(p->rinv, p->uinv, p->sp_zhost, p->tvec, m, mp, ns, w1, wA, s);
+  p->sp_ns_last = ns;
   tstop(p);
   const double add = predictive ? p->h.sigma2 : 0.0;
   const double sign = maximise ? 1.0 : -1.0;
@@ -2595,7 +2600,9 @@ void do_sample_paths_refine(gprhip_problem* p, const double* z, int64_t ldz, int
     for (int j = 0; j < nd; ++j) p->sp_zhost[(int64_t)i * SP_MAX_DRAWS + j] = z[(int64_t)j * ldz + i];
   double* const wA = p->sp_coef + (int64_t)mp * SP_MAX_DRAWS;
   tstart(p, "sp_coeff");
+  p->sp_ns_last = 0;
   launch_sp_weights(p->rinv, p->uinv, p->sp_zhost, p->tvec, m, mp, nd, p->sp_coef, wA, s);
+  p->sp_ns_last = nd;
   tstop(p);
   // the persistent kernel keeps its state in the caller's device buffers where there are some
   const bool direct = !proj && on_device;
@@ -2990,6 +2997,7 @@ void do_load_predictor(gprhip_problem* p, const gprhip_hypers* h, const double* 
   p->multi_state = false;
   p->cond_km = -1.0;
   p->pg_m_valid = false;
+  p->sp_ns_last = 0;
   upload_hypers(p, h);
   std::vector<double> t(mp, 0.0);
   if (coeffs) std::memcpy(t.data(), coeffs, (size_t)m * sizeof(double));
@@ -4279,6 +4287,32 @@ int gprhip_debug_fetch(gprhip_problem* p, const char* name, double* out, int64_t
       GPR_HIP(hipStreamSynchronize(p->stream));
       for (int64_t c = 0; c < w; ++c)
         for (int64_t r = 0; r < w; ++r) out[(size_t)(c * w + r)] = h[(size_t)(r * mp + c)];
+      return;
+    }
+    else if (nm == "sp_a") {
+      // the weights A = t 1^T + U^-1 (R~^-1 Z) of the last gprhip_sample_paths / gprhip_sample_paths_refine call, as
+      // sample_paths_kernel, path_grad_at_kernel and path_eval read them: the second half of sp_coef, [mp][64].  With "t",
+      // "uinv" and "rinv" the weights are a short contraction of operands a test holds exactly, and every output of the two
+      // calls one of the weights.  A copy only; nothing of the model state changes.
+      need_model(p, "gprhip_debug_fetch");
+      if (!p->sp_coef || p->sp_ns_last < 1) {
+        set_error("gprhip_debug_fetch: \"sp_a\" needs the weights of a gprhip_sample_paths or gprhip_sample_paths_refine "
+                  "call on the current model state");
+        throw HipFail{ST_STATE};
+      }
+      const int64_t m = p->m, mp = p->mp, ns = p->sp_ns_last;
+      if (len < m * ns) {
+        set_error("gprhip_debug_fetch: \"sp_a\" needs m doubles for each draw of that call");
+        throw HipFail{ST_BAD_ARG};
+      }
+      const bool padded = len >= mp * SP_MAX_DRAWS;  // mp*64 doubles: the padded block as it is stored
+      const int64_t rows = padded ? mp : m, cols = padded ? SP_MAX_DRAWS : ns;
+      GPR_HIP(hipSetDevice(p->device));
+      std::vector<double> h((size_t)mp * SP_MAX_DRAWS);
+      GPR_HIP(hipMemcpyAsync(h.data(), p->sp_coef + mp * SP_MAX_DRAWS, h.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+      GPR_HIP(hipStreamSynchronize(p->stream));
+      for (int64_t c = 0; c < cols; ++c)
+        for (int64_t r = 0; r < rows; ++r) out[(size_t)(c * rows + r)] = h[(size_t)(r * SP_MAX_DRAWS + c)];
       return;
     }
     else {

@@ -450,10 +450,12 @@ class Problem:
         dr = np.ascontiguousarray(draw_of, dtype=np.int32)
         if dr.shape != (ns,):
             raise ValueError("sample_paths_refine: draw_of takes %d entries" % ns)
+        self._sp_ns_last = 0  # (until the call returns: a call that raises may or may not have formed its weights)
         _lib.check(self._lib.gprhip_sample_paths_refine(self._handle(), _f64_ptr(z), self.m, nd, int(bool(maximise)), C.byref(opt),
                                                         *bptr, st_ptr, self.D, ns, dr.ctypes.data_as(C.POINTER(C.c_int)),
                                                         ptrs["x"], self.D, ptrs["values"], ptrs["dvalues"], self.D,
                                                         ptrs["evals"], ptrs["accepted"], ptrs["status"], ptrs["trace"], on_device))
+        self._sp_ns_last = nd  # (debug_fetch_matrix("sp_a"))
         return out
 
     def sample_paths(self, test_inputs, z, eps=None, predictive=False, maximise=True, top_k=0, want_samples=True,
@@ -514,8 +516,10 @@ class Problem:
             sp = C.c_void_p(out["samples"].ctypes.data) if want_samples else null
             ep = C.c_void_p(eps.ctypes.data) if eps is not None else null
             xt_ptr, on_device = C.c_void_p(xt.ctypes.data), 0
+        self._sp_ns_last = 0  # (until the call returns: a call that raises may or may not have formed its weights)
         _lib.check(self._lib.gprhip_sample_paths(self._handle(), _f64_ptr(z), self.m, ns, xt_ptr, self.D, nt, ep, nt,
                                                  int(bool(predictive)), sp, nt, int(bool(maximise)), top_k, *tops, on_device))
+        self._sp_ns_last = ns  # (debug_fetch_matrix("sp_a"))
         if top_k > 0:
             out.update(top_index=top_index, top_values=top_values, top_dvalues=top_dvalues)
         return out
@@ -655,10 +659,25 @@ class Problem:
         calls read them (m x m, upper triangle, zeros below; they need the factors of an evaluation or of a predictor loaded
         with co-variance coefficients); "pg_m": M = U^-1 (I - R~^-1 R~^-T) U^-T as the product G = K M of predict_input_grad
         and acquire reads it (m x m, full; available once such a call has formed it -- stage "pg_m" --, until the next
-        evaluation or load_predictor; `rows` = m rounded up to a multiple of 128 returns the padded matrix as it is stored)."""
+        evaluation or load_predictor; `rows` = m rounded up to a multiple of 128 returns the padded matrix as it is stored);
+        "sp_a": the weights A = t 1^T + U^-1 (R~^-1 Z) of the last sample_paths / sample_paths_refine call of this object, as
+        its kernels read them (m x ns of that call; a state error before any such call and after the next evaluation or
+        load_predictor; `rows` = m rounded up to a multiple of 128 returns the padded rows x 64 block as it is stored).  For "pg_m" and "sp_a" any other `rows` than m or that
+        padded count is a ValueError: the library tells the two layouts apart by the length alone."""
+        if name in ("pg_m", "sp_a"):
+            # the library picks the padded or the plain layout from the length alone: only the two row counts it knows pass
+            mp = -(-self.m // 128) * 128
+            if rows is not None and int(rows) not in (self.m, mp):
+                raise ValueError("debug_fetch_matrix: %r takes rows = %d (the default) or %d (padded)" % (name, self.m, mp))
+            padded = rows is not None and int(rows) == mp
         if name == "pg_m":
-            w = self.m if rows is None else int(rows)
+            w = mp if padded else self.m
             out = np.empty((w, w), dtype=np.float64, order="F")
+        elif name == "sp_a":
+            # the draw count of the last call that returned; 0 while a call is under way or after one that raised -- one column
+            # is asked for then, and the library, which holds the count too, refuses where that is not what it has
+            ns = getattr(self, "_sp_ns_last", 0) or 1
+            out = np.empty((mp, 64) if padded else (self.m, ns), dtype=np.float64, order="F")
         elif name in ("km", "w_mat", "uinv", "rinv"):
             out = np.empty((self.m, self.m), dtype=np.float64, order="F")
         elif name in ("knm_rows", "x_rows"):

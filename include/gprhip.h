@@ -600,6 +600,11 @@ int gprhip_condition(gprhip_problem* p, double* cond_km, double* coeff_error_bou
  *               points or more than 16 point dimensions (stage "pg_m"), until the next evaluation or gprhip_load_predictor
  *               (GPRHIP_ESTATE otherwise).  With len >= mp*mp, mp = m rounded up to a multiple of 128, the padded
  *               mp x mp matrix as it is stored.  A copy: the state is untouched.
+ *   "sp_a" m*ns : the weights A = t 1^T + U^-1 (R~^-1 Z) of the last gprhip_sample_paths or gprhip_sample_paths_refine call
+ *               as its kernels read them, Fortran m x ns with ns the draws of that call (the problem remembers the count) --
+ *               from that call until the next evaluation or gprhip_load_predictor (GPRHIP_ESTATE before any such call and
+ *               after either).  With len >= mp*64 the padded block as it is stored, Fortran mp x 64: rows >= m and columns
+ *               >= ns are zero.  A copy: the state is untouched.
  * Returns GPRHIP_EBADARG for an unknown name. */
 int gprhip_debug_fetch(gprhip_problem* p, const char* name, double* out, int64_t len);
 
