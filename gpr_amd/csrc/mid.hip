@@ -1207,7 +1207,7 @@ void launch_mid_pass2(const MidPass2Args& a, int col_rows, double* tile, double*
                       hipStream_t s) {
   mid_attrs();
   const int nmt = (1 + a.d + a.D + 15) / 16;
-  const int nproj = a.D * a.d;
+  const int nproj = (int)(tail - proj);  // the buffer's `Proj block: dbig x d of a Cov_se_fat layout, projection or not
   mid_by_tiles(a.mp, [&](auto mpv) {
     constexpr int MPV = decltype(mpv)::value;
     const int ng = mid_groups<MPV>(a.rows_p);

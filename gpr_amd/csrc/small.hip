@@ -208,7 +208,9 @@ __device__ __forceinline__ void small_reduce2_body(const double* __restrict__ pa
                                                    double* __restrict__ tail) {
   const int plen = p2len(d, D, ms), ncq = 1 + d + D + (ms ? d : 0);
   int idx = blockIdx.x * 256 + threadIdx.x;
-  const int ntile = TILE * TILE, ncol = col_rows * mp, nproj = D * d;
+  // nproj: the partials' `Proj entries (none without a projection); nprojbuf: the buffer's, which a Cov_se_fat layout has
+  // with or without one -- all of them are written
+  const int ntile = TILE * TILE, ncol = col_rows * mp, nproj = D * d, nprojbuf = (int)(tail - proj);
   int src = -1;
   double* dst;
   if (idx < ntile) {
@@ -219,10 +221,10 @@ __device__ __forceinline__ void small_reduce2_body(const double* __restrict__ pa
     const int q = idx / mp, c = idx % mp;
     dst = colblk + idx;
     if (q < ncq && c < SM) src = SM * SM + q * SM + c;
-  } else if ((idx -= ncol) < nproj) {
+  } else if ((idx -= ncol) < nprojbuf) {
     dst = proj + idx;
-    src = SM * SM + ncq * SM + idx;
-  } else if ((idx -= nproj) < 8) {
+    if (idx < nproj) src = SM * SM + ncq * SM + idx;
+  } else if ((idx -= nprojbuf) < 8) {
     dst = tail + idx;
     src = SM * SM + ncq * SM + nproj + idx;
   } else {
@@ -469,7 +471,9 @@ void launch_small_pass2_batch(const SmallPass2Args& a0, int col_rows, const Smal
     else if (a0.D <= 16) hipLaunchKernelGGL((small_pass2_batch_kernel<DT, 16, false>), grid, dim3(256), small_lds2(DT), s, d_lanes, stride);
     else hipLaunchKernelGGL((small_pass2_batch_kernel<DT, 64, false>), grid, dim3(256), small_lds2(DT), s, d_lanes, stride);
   });
-  const int nout = TILE * TILE + col_rows * a0.mp + a0.D * a0.d + 8;
+  // the buffer's `Proj block is dbig x d, projection or not: col_rows = d + 1 (Cov_se_iso, dbig = 0) or d + 1 + dbig + d
+  const int dbig = col_rows > a0.d + 1 ? col_rows - 1 - 2 * a0.d : 0;
+  const int nout = TILE * TILE + col_rows * a0.mp + dbig * a0.d + 8;
   hipLaunchKernelGGL(small_reduce2_batch_kernel, dim3((nout + 255) / 256, count), dim3(256), 0, s, d_red, stride);
   GPR_HIP(hipGetLastError());
 }
@@ -514,7 +518,7 @@ void launch_small_pass2(const SmallPass2Args& a, int col_rows, double* tile, dou
     else if (a.D <= 16) hipLaunchKernelGGL((small_pass2_kernel<DT, 16, false>), dim3(ng), dim3(256), small_lds2(DT), s, a);
     else hipLaunchKernelGGL((small_pass2_kernel<DT, 64, false>), dim3(ng), dim3(256), small_lds2(DT), s, a);
   });
-  const int nout = TILE * TILE + col_rows * a.mp + a.D * a.d + 8;
+  const int nout = TILE * TILE + col_rows * a.mp + (int)(tail - proj) + 8;  // (the buffer's `Proj block: dbig x d, projection or not)
   hipLaunchKernelGGL(small_reduce2_kernel, dim3((nout + 255) / 256), dim3(256), 0, s, a.part, ng, a.mp, a.d, a.D, ms ? 1 : 0,
                      col_rows, tile, colblk, proj, tail);
   GPR_HIP(hipGetLastError());

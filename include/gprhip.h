@@ -237,6 +237,21 @@ int64_t gprhip_ar2_len(const gprhip_problem* p);
  * (r, c) of the symmetric m x m part that heads both buffers -- stored as its upper 128 x 128 tiles only, tile (bm <= bn)
  * at ((bn (bn + 1) / 2 + bm) * 128 * 128, row-major inside (r, c < m rounded up to 128; the tile of (r, c) must be on or
  * above the diagonal, else -1).  A host that owns the collective sizes and fills its buffers with these. */
+/* What the two buffers hold, mp = m rounded up to 128, E = X .* K_nm, all sums over the shard's rows:
+ *   exchange 1  [packed tiles of B~_part = V^T diag(1/s) V | c~ = V^T (y ./ s) (mp) | tail (4)]
+ *               tail: 0 sum log s, 1 sum y^2 / s, 2 sum r / s, 3 unused
+ *   exchange 2  [packed tiles of G~_part = V^T diag(v) V | column block (col_rows x mp) | `Proj second term (dbig x d) | tail (8)]
+ *               col_rows = d + 1 and dbig = 0 for Cov_se_iso; d + 1 + D + d and dbig = D for Cov_se_fat
+ *               column block rows: sum_r E_rc; sum_r p_kr E_rc (d rows); with a projection sum_r x_br E_rc (D rows); with
+ *               multiscales sum_r p_kr^2 E_rc (d rows) directly behind the rows before them; every further row zero
+ *               `Proj second term, big-major: sum_r x_br p_kr sum_c E_rc [/ ms_kc]; zero without a projection
+ *               tail: 0 sum v, 1 sum 1/s, 2 sum w res, 3 sum v1, 4 sum E, 5 sum E |p_r - z_c|^2 (read for Cov_se_iso only),
+ *               6, 7 unused
+ * A gradient evaluation writes every entry of both buffers, whatever they held; an evidence-only one writes all of exchange
+ * 1 and zeroes the tail of exchange 2 alone.  Entries of a tile with row or column >= m, entries of c~ and of the column block
+ * with column >= m, unused rows of the column block and unused tail slots are +0.0: they are summed with every other
+ * shard's.  Entries below the diagonal (r > c) of a diagonal tile are finite but otherwise unspecified (the mirror image, or
+ * zero, by kernel family), and pass 2 and the finish stage never read them. */
 int64_t gprhip_exchange_len(int cov_kind, int D, int d, int m, int which);
 int64_t gprhip_exchange_offset(int m, int r, int c);
 int gprhip_eval_pass1(gprhip_problem* p, const gprhip_hypers* h, int want_grad, int64_t n_total,

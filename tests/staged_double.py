@@ -20,6 +20,8 @@ import scipy.linalg as sl
 
 from oracle import fitc_oracle as O
 from gpr_amd.problem import Evaluation
+from tests.exchange_ref import (A1_ISR, A1_ISY2, A1_SUMLOGS, A1_TAIL, A2_SUME, A2_SUMED, A2_SUMIS, A2_SUMV, A2_SUMV1, A2_TAIL,
+                                A2_WRES)
 
 
 def _view(ptr, length):
@@ -38,7 +40,7 @@ class StagedDouble:
         self._pk_r, self._pk_c = rr, cc
         self._pk_off = np.array([self._lib.gprhip_exchange_offset(m, int(r), int(c)) for r, c in zip(rr, cc)], dtype=np.int64)
         assert self._pk_off.min() >= 0
-        self.packed = int(self._lib.gprhip_exchange_len(0, D, d, m, 1)) - self.mp - 4
+        self.packed = int(self._lib.gprhip_exchange_len(0, D, d, m, 1)) - self.mp - A1_TAIL
 
     def ar1_len(self):
         return int(self._lib.gprhip_exchange_len(0, self.D, self.d, self.m, 1))
@@ -88,7 +90,9 @@ class StagedDouble:
         self._pack(ar1, (V * self.is_[:, None]).T @ V)
         pk, mp = self.packed, self.mp
         ar1[pk:pk + m] = V.T @ (self.is_ * yy)
-        ar1[pk + mp:] = [np.sum(np.log(s)), np.sum(self.is_ * yy * yy), np.sum(self.is_ * self.r), 0.0]
+        tail = np.zeros(A1_TAIL)
+        tail[A1_SUMLOGS], tail[A1_ISY2], tail[A1_ISR] = np.sum(np.log(s)), np.sum(self.is_ * yy * yy), np.sum(self.is_ * self.r)
+        ar1[pk + mp:] = tail
 
     def eval_pass2(self, ar1_ptr, ar2_ptr):
         m, d = self.m, self.d
@@ -128,8 +132,11 @@ class StagedDouble:
         pk, mp = self.packed, self.mp
         colv = ar2[pk:pk + (d + 1) * mp].reshape(d + 1, mp)   # [d + 1][mp]: sum E, sum p_k E
         colv[:, :m] = col
-        ar2[pk + (d + 1) * mp:] = [v.sum(), self.is_.sum(), np.sum(w * res), v1.sum(), E.sum(),
-                                   np.sum(E * sq), 0.0, 0.0]
+        tail = np.zeros(A2_TAIL)
+        tail[A2_SUMV], tail[A2_SUMIS], tail[A2_WRES], tail[A2_SUMV1] = v.sum(), self.is_.sum(), np.sum(w * res), v1.sum()
+        tail[A2_SUME], tail[A2_SUMED] = E.sum(), np.sum(E * sq)
+        ar2[pk + (d + 1) * mp:] = tail
+        self.v, self.w, self.Xm = v, w, Xm          # (tests/test_exchange_host.py holds the buffers against these operands)
 
     def eval_finish(self, ar2_ptr):
         m, d = self.m, self.d
@@ -139,19 +146,19 @@ class StagedDouble:
         col = ar2[pk:pk + (d + 1) * mp].reshape(d + 1, mp)[:, :m]
         tail = ar2[pk + (d + 1) * mp:]
         logdet_bt = 2 * np.sum(np.log(np.diag(self.R)))
-        l1 = -0.5 * (logdet_bt + self.tail1[0] + self.n_total * O.LOG_2PI)
+        l1 = -0.5 * (logdet_bt + self.tail1[A1_SUMLOGS] + self.n_total * O.LOG_2PI)
         if self.variational:
-            l1 += -0.5 * self.tail1[2]
-        l2 = 0.0 if self.model_only else -0.5 * (self.tail1[1] - self.b @ self.b)
+            l1 += -0.5 * self.tail1[A1_ISR]
+        l2 = 0.0 if self.model_only else -0.5 * (self.tail1[A1_ISY2] - self.b @ self.b)
         if not self.want_grad:
             return Evaluation(l1, l2, l1 + l2, None, None, self.t.copy())
         Wt = np.eye(m) - self.binv - np.outer(self.tt, self.tt) - G
         W = self.Ui @ Wt @ self.Ui.T
-        dls2 = -0.5 * (tail[0] - tail[1] if self.variational else tail[0])
+        dls2 = -0.5 * (tail[A2_SUMV] - tail[A2_SUMIS] if self.variational else tail[A2_SUMV])
         iso = isinstance(self.k, O.SeIsoKernel)
         scale = self.k.inv_ell2 if iso else 1.0
         wk = W * self.km
-        g_sf2 = -0.5 * (self.k.sf2 * tail[0] - wk.sum()) - tail[4]
+        g_sf2 = -0.5 * (self.k.sf2 * tail[A2_SUMV] - wk.sum()) - tail[A2_SUME]
         zq = np.zeros((m, m))
         for i in range(d):
             df = self.Z[i, :][:, None] - self.Z[i, :][None, :]
@@ -161,7 +168,7 @@ class StagedDouble:
             zp = np.sum(wk * (self.Z[k_, :][:, None] - self.Z[k_, :][None, :]), axis=0)
             gi[:, k_] = scale * zp - scale * (col[k_ + 1] - self.Z[k_, :] * col[0])
         if iso:
-            g_ell = 0.5 * scale * np.sum(wk * zq) - scale * tail[5]
+            g_ell = 0.5 * scale * np.sum(wk * zq) - scale * tail[A2_SUMED]
             grad = np.concatenate([[g_ell, g_sf2], gi.reshape(-1)])
         else:
             grad = np.concatenate([[g_sf2], gi.reshape(-1)])
