@@ -296,7 +296,7 @@ struct gprhip_problem {
   int sp_ns_last = 0;  // draws of the weights the second half of sp_coef holds; 0: none of the current model state
   double *sp_f = nullptr, *sp_eps = nullptr;
   int64_t sp_f_rows = 0, sp_eps_rows = 0;
-  void* sp_scratch = nullptr;
+  char* sp_scratch = nullptr;
   int64_t sp_scratch_bytes = 0;
   double *sp_out = nullptr, *sp_host = nullptr;
   bool use_small() const {
@@ -1898,6 +1898,18 @@ void release_buf(gprhip_problem* p, T*& q) {
   q = nullptr;
 }
 
+// a buffer of the problem that a call needs `need` elements of (`have`: what it holds): regrown once the stream has drained;
+// the recorded size is zero while there is no buffer
+template <typename T>
+void grow_buf(gprhip_problem* p, T*& q, int64_t& have, int64_t need) {
+  if (have >= need) return;
+  GPR_HIP(hipStreamSynchronize(p->stream));
+  release_buf(p, q);
+  have = 0;
+  q = p->alloc<T>(need);
+  have = need;
+}
+
 // prediction scratch for chunks of `chunk` test points: the points, their projection and three row vectors
 void ensure_predict_scratch(gprhip_problem* p, int64_t chunk) {
   if (p->xt && p->xt_rows >= chunk) return;
@@ -2224,6 +2236,15 @@ void do_predict_input_grad(gprhip_problem* p, const double* test_inputs, int64_t
   if (p->timer.on) tcollect(p);
 }
 
+// the criterion needs the variance (the bound with kappa = 0 is the mean alone); the kernels' form of the criterion
+bool acq_wants_var(const gprhip_acquisition* acq) { return !(acq->kind == GPRHIP_ACQ_BOUND && acq->kappa == 0.0); }
+AcqArgs acq_args(const gprhip_acquisition* acq) {
+  AcqArgs q;
+  q.kind = acq->kind; q.s = acq->maximise ? 1.0 : -1.0; q.best = acq->best; q.xi = acq->xi; q.kappa = acq->kappa;
+  q.var_floor = acq->var_floor; q.values = nullptr;
+  return q;
+}
+
 // gprhip_acquire: the chunk loop of do_predict_input_grad with the criterion epilogue of the two kernels -- one value vector and
 // one gradient matrix instead of two --, and the best top_k candidates selected on the device chunk by chunk (acquire.hip),
 // the chunks' lists merged here with the same rule: value descending, the lower index first among equal values.
@@ -2231,7 +2252,7 @@ void do_predict_input_grad(gprhip_problem* p, const double* test_inputs, int64_t
 void do_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const double* test_inputs, int64_t ld, int64_t nt,
                 double* values, double* dvalues, int64_t ldg, double* means, double* variances, int top_k, int64_t* top_index,
                 double* top_values, double* top_dvalues, int on_device) {
-  const bool want_var = !(acq->kind == GPRHIP_ACQ_BOUND && acq->kappa == 0.0) || variances;
+  const bool want_var = acq_wants_var(acq) || variances;
   need_posterior_state(p, "gprhip_acquire", "predict from", true, want_var, true,
                        "means and their gradients are available after the next gprhip_eval");
   GPR_HIP(hipSetDevice(p->device));
@@ -2247,9 +2268,7 @@ void do_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const double* 
                           hipHostMallocDefault));
   }
   if (plan.mats) ensure_predict_m(p);
-  AcqArgs q;
-  q.kind = acq->kind; q.s = acq->maximise ? 1.0 : -1.0; q.best = acq->best; q.xi = acq->xi; q.kappa = acq->kappa;
-  q.var_floor = acq->var_floor;
+  AcqArgs q = acq_args(acq);
   const double add = acq->predictive ? p->h.sigma2 : 0.0;
   SpBest best;  // the best so far, over the chunks done
   walk_chunks(p, plan.chunk, test_inputs, ld, nt, on_device, [&](int64_t lo, int rows, int rows_p, const double*, const double* pts) {
@@ -2292,108 +2311,186 @@ void do_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const double* 
   if (p->timer.on) tcollect(p);
 }
 
+// ---- what gprhip_acquire_refine and gprhip_sample_paths_refine share: one arena (rf_buf), one library-side loop
+// The arena of a call with ns starts:  bnd (lower | upper | scale, [D] each) | Y X G GY ([ns][D] each) | A AY AL ([ns] each) |
+// n_int_vectors integer vectors [ns] (evals | accepted | status, and draw_of for the sample paths) | the staging of a host trace
+struct RefineWork {
+  int64_t ns, len, trace_len;  // starts; doubles of the arena; of them the staging of a host trace, the arena's tail
+  double *bnd, *Y, *X, *G, *GY, *A, *AY, *AL;
+  int* ints;
+  double* trace_dev;  // where the kernels write the trace: the caller's device buffer, the staging, or null
+};
+int64_t refine_work_len(int D, int64_t ns, int n_int_vectors, int64_t trace_len) {
+  return 3 * D + 4 * ns * D + 3 * ns + (n_int_vectors * ns + 1) / 2 + trace_len;
+}
+// the sizes of a call's arena, before anything is allocated: w.len doubles are counted in front of pg_prepare where rf_buf is shorter
+RefineWork refine_work_sizes(int D, int64_t ns, int n_int_vectors, int max_evals, const double* trace, int on_device) {
+  RefineWork w{};
+  w.ns = ns;
+  w.trace_len = (trace && !on_device) ? ns * max_evals * (2 * D + 3) : 0;
+  w.len = refine_work_len(D, ns, n_int_vectors, w.trace_len);
+  return w;
+}
+// grows rf_buf to w.len doubles, makes the pinned count where the library-side loop will read it, carves the arena up and
+// uploads the box, the scale and the caller's host trace
+void refine_work(gprhip_problem* p, RefineWork& w, const double* lower, const double* upper, const double* scale, double* trace,
+                 int on_device, bool host_loop) {
+  hipStream_t s = p->stream;
+  const int D = p->D;
+  const int64_t ns = w.ns, nsD = ns * D;
+  grow_buf(p, p->rf_buf, p->rf_len, w.len);
+  if (host_loop && !p->rf_active) GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->rf_active), sizeof(int), hipHostMallocDefault));
+  w.bnd = p->rf_buf;
+  w.Y = w.bnd + 3 * D; w.X = w.Y + nsD; w.G = w.X + nsD; w.GY = w.G + nsD;
+  w.A = w.GY + nsD; w.AY = w.A + ns; w.AL = w.AY + ns;
+  w.ints = reinterpret_cast<int*>(w.AL + ns);
+  w.trace_dev = trace ? (on_device ? trace : w.bnd + (w.len - w.trace_len)) : nullptr;
+  GPR_HIP(hipMemcpyAsync(w.bnd, lower, (size_t)D * 8, hipMemcpyHostToDevice, s));
+  GPR_HIP(hipMemcpyAsync(w.bnd + D, upper, (size_t)D * 8, hipMemcpyHostToDevice, s));
+  if (scale) GPR_HIP(hipMemcpyAsync(w.bnd + 2 * D, scale, (size_t)D * 8, hipMemcpyHostToDevice, s));
+  if (w.trace_len > 0)  // records that no evaluation writes keep what the caller's buffer holds
+    GPR_HIP(hipMemcpyAsync(w.trace_dev, trace, (size_t)w.trace_len * 8, hipMemcpyHostToDevice, s));
+}
+// hs clipped into the box, into Y
+void refine_upload_clipped(gprhip_problem* p, const RefineWork& w, std::vector<double>& hs, const double* lower, const double* upper) {
+  const int D = p->D;
+  for (size_t i = 0; i < hs.size(); ++i) hs[i] = refine_clip(hs[i], lower[i % D], upper[i % D]);
+  GPR_HIP(hipMemcpyAsync(w.Y, hs.data(), hs.size() * 8, hipMemcpyHostToDevice, p->stream));
+}
+RefineOpts refine_opts(const gprhip_refine_options* opt) {
+  RefineOpts o;
+  o.max_evals = opt->max_evals; o.step0 = opt->step0; o.c1 = opt->c1; o.shrink = opt->shrink; o.grow = opt->grow;
+  o.xtol = opt->xtol;
+  return o;
+}
+// the state of the ns starts in the arena
+RefineStepArgs refine_step_args(gprhip_problem* p, const RefineWork& w, bool scaled, const RefineOpts& o) {
+  const int D = p->D;
+  const int64_t ns = w.ns;
+  RefineStepArgs st;
+  st.ns = (int)ns; st.D = D; st.first = 1; st.lower = w.bnd; st.upper = w.bnd + D; st.scale = scaled ? w.bnd + 2 * D : nullptr;
+  st.o = o;
+  st.x = w.X; st.g = w.G; st.y = w.Y; st.gy = w.GY; st.ay = w.AY; st.a = w.A; st.alpha = w.AL;
+  st.evals = w.ints; st.accepted = w.ints + ns; st.status = w.ints + 2 * ns; st.trace = w.trace_dev; st.active = p->rf_active;
+  return st;
+}
+// a persistent kernel keeps the state in the caller's device buffers where there are some: nothing to copy afterwards
+void refine_state_in_place(RefineStepArgs& st, double* x_out, double* values, double* dvalues, int* evals, int* accepted, int* status) {
+  if (x_out) st.x = x_out;
+  if (dvalues) st.g = dvalues;
+  if (values) st.a = values;
+  if (evals) st.evals = evals;
+  if (accepted) st.accepted = accepted;
+  if (status) st.status = status;
+}
+// The library-side loop: per evaluation the chunk walk over the trial points st.y (ns fits one chunk) -- eval(ev, pts, rows,
+// rows_p) leaves the objective in st.ay and its gradient in st.gy --, then refine_step_kernel, which leaves the number of
+// starts that go on in pinned memory: one integer per evaluation comes back.
+template <typename F>
+void refine_host_loop(gprhip_problem* p, const PgPlan& plan, RefineStepArgs& st, F&& eval) {
+  for (int ev = 0; ev < st.o.max_evals; ++ev) {
+    st.first = ev == 0;
+    walk_chunks(p, plan.chunk, st.y, st.D, st.ns, 1, [&](int64_t, int rows, int rows_p, const double*, const double* pts) {
+      eval(ev, pts, rows, rows_p);
+      tstart(p, "rf_step");
+      launch_refine_step(st, p->stream);
+      tstop(p);
+    });
+    if (*static_cast<volatile int*>(p->rf_active) == 0) break;
+  }
+}
+// from where the kernels left the state (st) to the caller's buffers, where those are others
+void refine_copy_out(gprhip_problem* p, const RefineStepArgs& st, const RefineWork& w, double* x_out, int64_t ldx, double* values,
+                     double* dvalues, int64_t ldg, int* evals, int* accepted, int* status, double* trace, int on_device) {
+  hipStream_t s = p->stream;
+  const size_t ns = (size_t)st.ns, row = (size_t)st.D * 8;
+  const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const double* const mats[2] = {st.x, st.g};
+  double* const dst[2] = {x_out, dvalues};
+  const int64_t lds[2] = {ldx, ldg};
+  for (int j = 0; j < 2; ++j)
+    if (dst[j] && dst[j] != mats[j]) GPR_HIP(hipMemcpy2DAsync(dst[j], (size_t)lds[j] * 8, mats[j], row, row, ns, kind, s));
+  if (values && values != st.a) GPR_HIP(hipMemcpyAsync(values, st.a, ns * 8, kind, s));
+  int* const idst[3] = {evals, accepted, status};
+  const int* const isrc[3] = {st.evals, st.accepted, st.status};
+  for (int j = 0; j < 3; ++j)
+    if (idst[j] && idst[j] != isrc[j]) GPR_HIP(hipMemcpyAsync(idst[j], isrc[j], ns * sizeof(int), kind, s));
+  if (w.trace_len > 0) GPR_HIP(hipMemcpyAsync(trace, w.trace_dev, (size_t)w.trace_len * 8, hipMemcpyDeviceToHost, s));
+}
+
 // gprhip_acquire_refine: projected gradient ascent with Armijo backtracking from ns starts (refine_step.h is the rule).
 //   * at most 64 inducing points of at most 16 dimensions, no projection: one persistent kernel (refine.hip) -- the loop runs
 //     on the device;
-//   * every other shape: the loop runs here.  State and trial points stay in device buffers, an evaluation is the chunk walk
-//     of gprhip_acquire on them (ns fits one chunk), refine_step_kernel follows it and leaves the number of starts that go on
-//     in pinned memory: one integer per evaluation comes back.
+//   * every other shape: the loop runs here (refine_host_loop).  State and trial points stay in device buffers, an evaluation
+//     is the chunk walk of gprhip_acquire on them.
 // The caller has checked the arguments and the model state; hs: the starts on the host, [ns][D], finite.
 void do_acquire_refine(gprhip_problem* p, const gprhip_acquisition* acq, const gprhip_refine_options* opt, const double* lower,
                        const double* upper, const double* scale, const double* starts, std::vector<double>& hs, int64_t ns,
                        double* x_out, int64_t ldx, double* values, double* dvalues, int64_t ldg, int* evals, int* accepted,
                        int* status, double* trace, int on_device) {
   const char* const fn = "gprhip_acquire_refine";
-  const bool want_var = !(acq->kind == GPRHIP_ACQ_BOUND && acq->kappa == 0.0);
+  const bool want_var = acq_wants_var(acq);
   GPR_HIP(hipSetDevice(p->device));
   hipStream_t s = p->stream;
   const int D = p->D;
   const bool small = one_kernel_path(p) && !p->has_proj();
-  const int64_t rec = 2 * D + 3, nsD = ns * D;
-  const int64_t trace_len = (trace && !on_device) ? ns * opt->max_evals * rec : 0;
-  const int64_t len = 3 * D + 4 * nsD + 3 * ns + (3 * ns + 1) / 2 + trace_len;
-  const bool grow = p->rf_len < len;
-  const PgPlan plan = pg_prepare(p, fn, ns, want_var, false, true, grow ? len * 8 : 0);
-  if (grow) {
-    GPR_HIP(hipStreamSynchronize(s));
-    release_buf(p, p->rf_buf);
-    p->rf_len = 0;
-    p->rf_buf = p->alloc<double>(len);
-    p->rf_len = len;
-  }
-  if (!p->rf_active) GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->rf_active), sizeof(int), hipHostMallocDefault));
-  double* const bnd = p->rf_buf;
-  double *const Y = bnd + 3 * D, *const X = Y + nsD, *const G = X + nsD, *const GY = G + nsD;
-  double *const A = GY + nsD, *const AY = A + ns, *const AL = AY + ns;
-  int* const ints = reinterpret_cast<int*>(AL + ns);
-  double* const trace_dev = trace ? (on_device ? trace : AL + ns + (3 * ns + 1) / 2) : nullptr;
-  GPR_HIP(hipMemcpyAsync(bnd, lower, (size_t)D * 8, hipMemcpyHostToDevice, s));
-  GPR_HIP(hipMemcpyAsync(bnd + D, upper, (size_t)D * 8, hipMemcpyHostToDevice, s));
-  if (scale) GPR_HIP(hipMemcpyAsync(bnd + 2 * D, scale, (size_t)D * 8, hipMemcpyHostToDevice, s));
-  if (trace && !on_device)  // records that no evaluation writes keep what the caller's buffer holds
-    GPR_HIP(hipMemcpyAsync(trace_dev, trace, (size_t)trace_len * 8, hipMemcpyHostToDevice, s));
-  RefineOpts o;
-  o.max_evals = opt->max_evals; o.step0 = opt->step0; o.c1 = opt->c1; o.shrink = opt->shrink; o.grow = opt->grow;
-  o.xtol = opt->xtol;
-  AcqArgs q;
-  q.kind = acq->kind; q.s = acq->maximise ? 1.0 : -1.0; q.best = acq->best; q.xi = acq->xi; q.kappa = acq->kappa;
-  q.var_floor = acq->var_floor; q.values = nullptr;
+  RefineWork w = refine_work_sizes(D, ns, 3, opt->max_evals, trace, on_device);
+  const PgPlan plan = pg_prepare(p, fn, ns, want_var, false, true, p->rf_len < w.len ? w.len * 8 : 0);
+  refine_work(p, w, lower, upper, scale, trace, on_device, true);
+  RefineStepArgs st = refine_step_args(p, w, scale != nullptr, refine_opts(opt));
+  AcqArgs q = acq_args(acq);
   const double add = acq->predictive ? p->h.sigma2 : 0.0;
   if (small) {
     const bool direct = on_device != 0;  // the kernel reads and writes the caller's device buffers
-    if (!direct) GPR_HIP(hipMemcpyAsync(Y, hs.data(), (size_t)nsD * 8, hipMemcpyHostToDevice, s));
+    if (direct) refine_state_in_place(st, x_out, values, dvalues, evals, accepted, status);
+    else GPR_HIP(hipMemcpyAsync(w.Y, hs.data(), (size_t)ns * D * 8, hipMemcpyHostToDevice, s));
     SmallPredictGradArgs a{};
-    a.cp = p->cp; a.pts = direct ? starts : Y; a.Z = p->Z; a.shift = p->zshift; a.uinv = p->uinv; a.rinv = p->rinv;
+    a.cp = p->cp; a.pts = direct ? starts : w.Y; a.Z = p->Z; a.shift = p->zshift; a.uinv = p->uinv; a.rinv = p->rinv;
     a.tvec = p->tvec; a.rows = (int)ns; a.m = p->m; a.mp = p->mp; a.d = p->d; a.want_var = want_var ? 1 : 0; a.add = add;
-    SmallRefineArgs rf;
-    rf.lower = bnd; rf.upper = bnd + D; rf.scale = scale ? bnd + 2 * D : nullptr; rf.o = o;
-    rf.x_out = direct ? x_out : (x_out ? X : nullptr);
-    rf.values = direct ? values : (values ? A : nullptr);
-    rf.dvalues = direct ? dvalues : (dvalues ? G : nullptr);
-    rf.evals = direct ? evals : (evals ? ints : nullptr);
-    rf.accepted = direct ? accepted : (accepted ? ints + ns : nullptr);
-    rf.status = direct ? status : (status ? ints + 2 * ns : nullptr);
-    rf.trace = trace_dev;
+    SmallRefineArgs rf;  // (an output that is not wanted is not stored)
+    rf.lower = st.lower; rf.upper = st.upper; rf.scale = st.scale; rf.o = st.o;
+    rf.x_out = x_out ? st.x : nullptr; rf.values = values ? st.a : nullptr; rf.dvalues = dvalues ? st.g : nullptr;
+    rf.evals = evals ? st.evals : nullptr; rf.accepted = accepted ? st.accepted : nullptr;
+    rf.status = status ? st.status : nullptr; rf.trace = w.trace_dev;
     tstart(p, "rf_small");
     launch_small_refine(a, q, rf, s);
     tstop(p);
   } else {
-    for (int64_t i = 0; i < nsD; ++i) hs[i] = refine_clip(hs[i], lower[i % D], upper[i % D]);
-    GPR_HIP(hipMemcpyAsync(Y, hs.data(), (size_t)nsD * 8, hipMemcpyHostToDevice, s));
+    refine_upload_clipped(p, w, hs, lower, upper);
     if (plan.mats) ensure_predict_m(p);
-    RefineStepArgs st;
-    st.ns = (int)ns; st.D = D; st.lower = bnd; st.upper = bnd + D; st.scale = scale ? bnd + 2 * D : nullptr; st.o = o;
-    st.x = X; st.g = G; st.y = Y; st.gy = GY; st.ay = AY; st.a = A; st.alpha = AL;
-    st.evals = ints; st.accepted = ints + ns; st.status = ints + 2 * ns; st.trace = trace_dev; st.active = p->rf_active;
-    q.values = AY;
-    for (int ev = 0; ev < o.max_evals; ++ev) {
-      st.first = ev == 0;
-      walk_chunks(p, plan.chunk, Y, D, ns, 1, [&](int64_t, int rows, int rows_p, const double*, const double* pts) {
-        double* const dsts[2] = {GY, nullptr};
-        pg_chunk(p, plan, pts, rows, rows_p, want_var, add, nullptr, nullptr, dsts, &q);
-        tstart(p, "rf_step");
-        launch_refine_step(st, s);
-        tstop(p);
-      });
-      if (*static_cast<volatile int*>(p->rf_active) == 0) break;
-    }
+    q.values = w.AY;
+    refine_host_loop(p, plan, st, [&](int, const double* pts, int rows, int rows_p) {
+      double* const dsts[2] = {w.GY, nullptr};
+      pg_chunk(p, plan, pts, rows, rows_p, want_var, add, nullptr, nullptr, dsts, &q);
+    });
   }
-  if (!(small && on_device)) {  // from the library's buffers to the caller's
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const double* const mats[2] = {X, G};
-    double* const dst[2] = {x_out, dvalues};
-    const int64_t lds[2] = {ldx, ldg};
-    for (int j = 0; j < 2; ++j)
-      if (dst[j])
-        GPR_HIP(hipMemcpy2DAsync(dst[j], (size_t)lds[j] * 8, mats[j], (size_t)D * 8, (size_t)D * 8, (size_t)ns, kind, s));
-    if (values) GPR_HIP(hipMemcpyAsync(values, A, (size_t)ns * 8, kind, s));
-    int* const idst[3] = {evals, accepted, status};
-    for (int j = 0; j < 3; ++j)
-      if (idst[j]) GPR_HIP(hipMemcpyAsync(idst[j], ints + j * ns, (size_t)ns * sizeof(int), kind, s));
-    if (trace && !on_device) GPR_HIP(hipMemcpyAsync(trace, trace_dev, (size_t)trace_len * 8, hipMemcpyDeviceToHost, s));
-  }
+  refine_copy_out(p, st, w, x_out, ldx, values, dvalues, ldg, evals, accepted, status, trace, on_device);
   GPR_HIP(hipStreamSynchronize(s));
   if (p->timer.on) tcollect(p);
+}
+
+// The weights A = t 1^T + U^-1 (R~^-1 Z) of gprhip_sample_paths and gprhip_sample_paths_refine, formed once per call.
+// path_weights_bytes: the device memory path_weights will allocate, for the count in front of pg_prepare.
+int64_t path_weights_bytes(const gprhip_problem* p) { return p->sp_coef ? 0 : 2 * (int64_t)p->mp * SP_MAX_DRAWS * 8; }
+// z: nd normal draws of m entries on the host (draw j at z + j ldz).  Returns A, [mp][SP_MAX_DRAWS] (the second half of sp_coef).
+double* path_weights(gprhip_problem* p, const double* z, int64_t ldz, int nd) {
+  const int m = p->m, mp = p->mp;
+  // (the pinned buffer first: a failure leaves both pointers null.  The weight kernel reads it by its host address, as
+  //  ship_kernel writes res_host: mapped, portable pinned memory has one address on host and device here)
+  if (!p->sp_zhost)
+    GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->sp_zhost), (size_t)mp * SP_MAX_DRAWS * sizeof(double),
+                          hipHostMallocPortable | hipHostMallocMapped));
+  if (!p->sp_coef) p->sp_coef = p->alloc<double>(2 * (int64_t)mp * SP_MAX_DRAWS);
+  // R~^-1 Z first, then U^-1 times it, plus t
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j < nd; ++j) p->sp_zhost[(int64_t)i * SP_MAX_DRAWS + j] = z[(int64_t)j * ldz + i];
+  double* const wA = p->sp_coef + (int64_t)mp * SP_MAX_DRAWS;
+  tstart(p, "sp_coeff");
+  p->sp_ns_last = 0;
+  launch_sp_weights(p->rinv, p->uinv, p->sp_zhost, p->tvec, m, mp, nd, p->sp_coef, wA, p->stream);
+  p->sp_ns_last = nd;
+  tstop(p);
+  return wA;
 }
 
 // gprhip_sample_paths: ns draws of the posterior as functions, evaluated at nt test points chunk by chunk
@@ -2418,7 +2515,7 @@ void do_sample_paths(gprhip_problem* p, const double* z, int64_t ldz, int ns, co
   const int64_t out_stride = (int64_t)top_k * (D + 2);
   const int64_t scratch_need = top_k > 0 ? acq_select_many_scratch_bytes(std::min(rows_need, piece_rows), top_k, ns) : 0;
   int64_t extra = 0;
-  if (!p->sp_coef) extra += 2 * (int64_t)mp * SP_MAX_DRAWS * 8;
+  extra += path_weights_bytes(p);
   if (stage_f && p->sp_f_rows < ns * rows_need) extra += ns * rows_need * 8;
   if (stage_e && p->sp_eps_rows < ns * rows_need) extra += ns * rows_need * 8;
   if (top_k > 0) {
@@ -2426,50 +2523,17 @@ void do_sample_paths(gprhip_problem* p, const double* z, int64_t ldz, int ns, co
     if (!p->sp_out) extra += (int64_t)SP_MAX_DRAWS * ACQ_MAX_TOP_K * (D + 2) * 8;
   }
   const PgPlan plan = pg_prepare(p, "gprhip_sample_paths", nt, resid, false, false, extra);
-  // (the pinned buffer first: a failure leaves both pointers null.  The weight kernel reads it by its host address, as
-  //  ship_kernel writes res_host: mapped, portable pinned memory has one address on host and device here)
-  if (!p->sp_zhost)
-    GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->sp_zhost), (size_t)mp * SP_MAX_DRAWS * sizeof(double),
-                          hipHostMallocPortable | hipHostMallocMapped));
-  if (!p->sp_coef) p->sp_coef = p->alloc<double>(2 * (int64_t)mp * SP_MAX_DRAWS);
-  if (stage_f && p->sp_f_rows < ns * rows_need) {
-    GPR_HIP(hipStreamSynchronize(s));
-    release_buf(p, p->sp_f);
-    p->sp_f_rows = 0;
-    p->sp_f = p->alloc<double>(ns * rows_need);
-    p->sp_f_rows = ns * rows_need;
-  }
-  if (stage_e && p->sp_eps_rows < ns * rows_need) {
-    GPR_HIP(hipStreamSynchronize(s));
-    release_buf(p, p->sp_eps);
-    p->sp_eps_rows = 0;
-    p->sp_eps = p->alloc<double>(ns * rows_need);
-    p->sp_eps_rows = ns * rows_need;
-  }
+  double* const wA = path_weights(p, z, ldz, ns);
+  if (stage_f) grow_buf(p, p->sp_f, p->sp_f_rows, ns * rows_need);
+  if (stage_e) grow_buf(p, p->sp_eps, p->sp_eps_rows, ns * rows_need);
   if (top_k > 0) {
-    if (p->sp_scratch_bytes < scratch_need) {
-      GPR_HIP(hipStreamSynchronize(s));
-      release_buf(p, p->sp_scratch);
-      p->sp_scratch_bytes = 0;
-      p->sp_scratch = p->alloc<char>(scratch_need);
-      p->sp_scratch_bytes = scratch_need;
-    }
+    grow_buf(p, p->sp_scratch, p->sp_scratch_bytes, scratch_need);
     if (!p->sp_out) {
       const int64_t len = (int64_t)SP_MAX_DRAWS * ACQ_MAX_TOP_K * (D + 2);
       p->sp_out = p->alloc<double>(len);
       GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->sp_host), (size_t)len * sizeof(double), hipHostMallocDefault));
     }
   }
-  // the weights, once per call: R~^-1 Z first, then U^-1 times it, plus t
-  for (int i = 0; i < m; ++i)
-    for (int j = 0; j < ns; ++j) p->sp_zhost[(int64_t)i * SP_MAX_DRAWS + j] = z[(int64_t)j * ldz + i];
-  double* const w1 = p->sp_coef;
-  double* const wA = p->sp_coef + (int64_t)mp * SP_MAX_DRAWS;
-  tstart(p, "sp_coeff");
-  p->sp_ns_last = 0;
-  launch_sp_weights(p->rinv, p->uinv, p->sp_zhost, p->tvec, m, mp, ns, w1, wA, s);
-  p->sp_ns_last = ns;
-  tstop(p);
   const double add = predictive ? p->h.sigma2 : 0.0;
   const double sign = maximise ? 1.0 : -1.0;
   const bool want_g = top_k > 0 && top_dvalues;
@@ -2557,105 +2621,40 @@ void do_sample_paths_refine(gprhip_problem* p, const double* z, int64_t ldz, int
   const char* const fn = "gprhip_sample_paths_refine";
   GPR_HIP(hipSetDevice(p->device));
   hipStream_t s = p->stream;
-  const int D = p->D, d = p->d, m = p->m, mp = p->mp;
+  const int D = p->D, d = p->d;
   const bool proj = p->has_proj();
-  const int64_t rec = 2 * D + 3, nsD = ns * D;
-  const int64_t trace_len = (trace && !on_device) ? ns * opt->max_evals * rec : 0;
-  const int64_t len = 3 * D + 4 * nsD + 3 * ns + (4 * ns + 1) / 2 + trace_len;
-  const bool grow = p->rf_len < len;
-  int64_t extra = grow ? len * 8 : 0;
-  if (!p->sp_coef) extra += 2 * (int64_t)mp * SP_MAX_DRAWS * 8;
-  const PgPlan plan = pg_prepare(p, fn, ns, false, false, true, extra);
+  RefineWork w = refine_work_sizes(D, ns, 4, opt->max_evals, trace, on_device);
+  const PgPlan plan = pg_prepare(p, fn, ns, false, false, true, (p->rf_len < w.len ? w.len * 8 : 0) + path_weights_bytes(p));
   if (proj && plan.chunk < ns) {  // (a chunk holds every count of starts the call accepts)
     set_error(std::string(fn) + ": the starts do not fit one chunk of test points");
     throw HipFail{ST_BAD_ARG};
   }
-  if (grow) {
-    GPR_HIP(hipStreamSynchronize(s));
-    release_buf(p, p->rf_buf);
-    p->rf_len = 0;
-    p->rf_buf = p->alloc<double>(len);
-    p->rf_len = len;
-  }
-  if (proj && !p->rf_active) GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->rf_active), sizeof(int), hipHostMallocDefault));
-  if (!p->sp_zhost)
-    GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->sp_zhost), (size_t)mp * SP_MAX_DRAWS * sizeof(double),
-                          hipHostMallocPortable | hipHostMallocMapped));
-  if (!p->sp_coef) p->sp_coef = p->alloc<double>(2 * (int64_t)mp * SP_MAX_DRAWS);
-  double* const bnd = p->rf_buf;
-  double *const Y = bnd + 3 * D, *const X = Y + nsD, *const G = X + nsD, *const GY = G + nsD;
-  double *const A = GY + nsD, *const AY = A + ns, *const AL = AY + ns;
-  int* const ints = reinterpret_cast<int*>(AL + ns);  // evals | accepted | status | draw_of
-  double* const trace_dev = trace ? (on_device ? trace : AL + ns + (4 * ns + 1) / 2) : nullptr;
-  GPR_HIP(hipMemcpyAsync(bnd, lower, (size_t)D * 8, hipMemcpyHostToDevice, s));
-  GPR_HIP(hipMemcpyAsync(bnd + D, upper, (size_t)D * 8, hipMemcpyHostToDevice, s));
-  if (scale) GPR_HIP(hipMemcpyAsync(bnd + 2 * D, scale, (size_t)D * 8, hipMemcpyHostToDevice, s));
-  GPR_HIP(hipMemcpyAsync(ints + 3 * ns, draw_of, (size_t)ns * sizeof(int), hipMemcpyHostToDevice, s));
-  if (trace && !on_device)  // records that no evaluation writes keep what the caller's buffer holds
-    GPR_HIP(hipMemcpyAsync(trace_dev, trace, (size_t)trace_len * 8, hipMemcpyHostToDevice, s));
-  for (int64_t i = 0; i < nsD; ++i) hs[i] = refine_clip(hs[i], lower[i % D], upper[i % D]);
-  GPR_HIP(hipMemcpyAsync(Y, hs.data(), (size_t)nsD * 8, hipMemcpyHostToDevice, s));
-  // the weights, once per call: R~^-1 Z first, then U^-1 times it, plus t
-  for (int i = 0; i < m; ++i)
-    for (int j = 0; j < nd; ++j) p->sp_zhost[(int64_t)i * SP_MAX_DRAWS + j] = z[(int64_t)j * ldz + i];
-  double* const wA = p->sp_coef + (int64_t)mp * SP_MAX_DRAWS;
-  tstart(p, "sp_coeff");
-  p->sp_ns_last = 0;
-  launch_sp_weights(p->rinv, p->uinv, p->sp_zhost, p->tvec, m, mp, nd, p->sp_coef, wA, s);
-  p->sp_ns_last = nd;
-  tstop(p);
-  // the persistent kernel keeps its state in the caller's device buffers where there are some
-  const bool direct = !proj && on_device;
-  RefineStepArgs st;
-  st.ns = (int)ns; st.D = D; st.first = 1; st.lower = bnd; st.upper = bnd + D; st.scale = scale ? bnd + 2 * D : nullptr;
-  st.o.max_evals = opt->max_evals; st.o.step0 = opt->step0; st.o.c1 = opt->c1; st.o.shrink = opt->shrink;
-  st.o.grow = opt->grow; st.o.xtol = opt->xtol;
-  st.x = (direct && x_out) ? x_out : X; st.g = (direct && dvalues) ? dvalues : G; st.y = Y; st.gy = GY; st.ay = AY;
-  st.a = (direct && values) ? values : A; st.alpha = AL;
-  st.evals = (direct && evals) ? evals : ints; st.accepted = (direct && accepted) ? accepted : ints + ns;
-  st.status = (direct && status) ? status : ints + 2 * ns;
-  st.trace = trace_dev; st.active = p->rf_active;
+  refine_work(p, w, lower, upper, scale, trace, on_device, proj);
+  int* const draw_dev = w.ints + 3 * ns;
+  GPR_HIP(hipMemcpyAsync(draw_dev, draw_of, (size_t)ns * sizeof(int), hipMemcpyHostToDevice, s));
+  refine_upload_clipped(p, w, hs, lower, upper);
+  const double* const wA = path_weights(p, z, ldz, nd);
+  RefineStepArgs st = refine_step_args(p, w, scale != nullptr, refine_opts(opt));
+  if (!proj && on_device) refine_state_in_place(st, x_out, values, dvalues, evals, accepted, status);
   PathEvalArgs e;
-  e.pts = Y; e.Z = p->Z; e.shift = p->zshift; e.W = wA; e.draw_of = ints + 3 * ns; e.status = st.status;
-  e.rows = (int)ns; e.m = m; e.d = d; e.nd = nd; e.log_sf2 = p->cp.log_sf2; e.inv_ell2_05 = p->cp.inv_ell2_05;
-  e.sign = maximise ? 1.0 : -1.0; e.val = AY; e.grad = GY; e.ldg = D;
+  e.pts = w.Y; e.Z = p->Z; e.shift = p->zshift; e.W = wA; e.draw_of = draw_dev; e.status = st.status;
+  e.rows = (int)ns; e.m = p->m; e.d = d; e.nd = nd; e.log_sf2 = p->cp.log_sf2; e.inv_ell2_05 = p->cp.inv_ell2_05;
+  e.sign = maximise ? 1.0 : -1.0; e.val = w.AY; e.grad = w.GY; e.ldg = D;
   if (!proj) {
     tstart(p, "prf_kernel");
     launch_path_refine(e, st, s);
     tstop(p);
   } else {
     e.grad = plan.stage_p[0]; e.ldg = d;
-    for (int ev = 0; ev < st.o.max_evals; ++ev) {
-      st.first = ev == 0;
-      e.status = ev == 0 ? nullptr : st.status;
-      walk_chunks(p, plan.chunk, Y, D, ns, 1, [&](int64_t, int rows, int, const double*, const double* pts) {
-        tstart(p, "prf_eval");
-        e.pts = pts;
-        launch_path_eval(e, s);
-        launch_input_grad_project(e.grad, rows, d, D, p->tproj, GY, D, s);
-        tstop(p);
-        tstart(p, "rf_step");
-        launch_refine_step(st, s);
-        tstop(p);
-      });
-      if (*static_cast<volatile int*>(p->rf_active) == 0) break;
-    }
+    refine_host_loop(p, plan, st, [&](int ev, const double* pts, int rows, int) {
+      tstart(p, "prf_eval");
+      e.pts = pts; e.status = ev == 0 ? nullptr : st.status;
+      launch_path_eval(e, s);
+      launch_input_grad_project(e.grad, rows, d, D, p->tproj, w.GY, D, s);
+      tstop(p);
+    });
   }
-  {  // from the library's buffers to the caller's
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const double* const mats[2] = {st.x, st.g};
-    double* const dst[2] = {x_out, dvalues};
-    const int64_t lds[2] = {ldx, ldg};
-    for (int j = 0; j < 2; ++j)
-      if (dst[j] && dst[j] != mats[j])
-        GPR_HIP(hipMemcpy2DAsync(dst[j], (size_t)lds[j] * 8, mats[j], (size_t)D * 8, (size_t)D * 8, (size_t)ns, kind, s));
-    if (values && values != st.a) GPR_HIP(hipMemcpyAsync(values, st.a, (size_t)ns * 8, kind, s));
-    int* const idst[3] = {evals, accepted, status};
-    const int* const isrc[3] = {st.evals, st.accepted, st.status};
-    for (int j = 0; j < 3; ++j)
-      if (idst[j] && idst[j] != isrc[j]) GPR_HIP(hipMemcpyAsync(idst[j], isrc[j], (size_t)ns * sizeof(int), kind, s));
-    if (trace && !on_device) GPR_HIP(hipMemcpyAsync(trace, trace_dev, (size_t)trace_len * 8, hipMemcpyDeviceToHost, s));
-  }
+  refine_copy_out(p, st, w, x_out, ldx, values, dvalues, ldg, evals, accepted, status, trace, on_device);
   GPR_HIP(hipStreamSynchronize(s));
   if (p->timer.on) tcollect(p);
 }
@@ -4010,7 +4009,7 @@ int gprhip_acquire_refine(gprhip_problem* p, const gprhip_acquisition* acq, cons
     if (p->d > 64) refuse("at most 64 point dimensions on the kernel side (d)");
     check_refine_box(fn, p, lower, upper, scale, ld, x_out, ldx, dvalues, ldg, on_device);
     // the model state before the starts are read back from the device: a refused call enqueues nothing
-    need_posterior_state(p, fn, "predict from", true, !(acq->kind == GPRHIP_ACQ_BOUND && acq->kappa == 0.0), true,
+    need_posterior_state(p, fn, "predict from", true, acq_wants_var(acq), true,
                          "means and their gradients are available after the next gprhip_eval");
     std::vector<double> hs = refine_starts(fn, p, starts, ld, ns, on_device);
     do_acquire_refine(p, acq, opt, lower, upper, scale, starts, hs, ns, x_out, ldx, values, dvalues, ldg, evals, accepted, status,

@@ -358,20 +358,8 @@ struct SmallRefineArgs {
 // starts, 64 per workgroup; U^-1, R~^-1, Z - s and t are staged once and the evaluation loop runs inside the kernel.  Of `a`,
 // means / vars / dmeans / dvars / ldg are not used.
 void launch_small_refine(const SmallPredictGradArgs& a, const AcqArgs& q, const SmallRefineArgs& rf, hipStream_t s);
-// The step of the library-side loop: one start per thread on [ns][D] device arrays.  first: (ay, gy) is the evaluation at the
-// clipped starts in y (x, g, st_* are initialised from it), else at the trial points y.  y receives the next trial points;
-// *active (pinned host memory, device-visible) the number of starts that go on.  One workgroup, no atomics.
-struct RefineStepArgs {
-  int ns, D, first;
-  const double *lower, *upper, *scale;  // [D] (device); scale may be null
-  RefineOpts o;
-  double *x, *g, *y;                    // [ns][D]
-  const double *gy, *ay;                // [ns][D], [ns]
-  double *a, *alpha;                    // [ns]
-  int *evals, *accepted, *status;       // [ns]
-  double* trace;                        // or null
-  int* active;
-};
+// The step of the library-side loop: refine_step_start (refine_step.h) for every start, one per thread, on the [ns][D] device
+// arrays of RefineStepArgs; *a.active receives the number of starts that go on.  One workgroup, no atomics.
 void launch_refine_step(const RefineStepArgs& a, hipStream_t s);
 
 // ---- posterior sample paths (sample_paths.hip): a draw is f(x) = sum_c k(x, z_c) a_c with the weights a = t + U^-1 R~^-1 z

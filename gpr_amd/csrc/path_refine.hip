@@ -10,8 +10,9 @@
 //     own draw only: a start's bits do not depend on what shares its wavefront or workgroup, nor on the width of the panel.
 //   * path_refine_kernel (no projection, any m, d <= 64): one persistent kernel, 64 starts per workgroup.  The state of a
 //     start is the [ns][D] arrays of the library-side loop (RefineStepArgs), in device memory and touched by one workgroup
-//     only; after an evaluation one lane per start runs the serial functions of refine_step.h on it -- the rule is not written
-//     again for another lane layout -- and the loop goes on until __syncthreads_or says that no start of the workgroup does.
+//     only; after an evaluation one lane per start runs refine_step_start of refine_step.h on it -- neither the rule nor its
+//     driver is written again: refine_step_kernel calls the same function -- and the loop goes on until __syncthreads_or
+//     says that no start of the workgroup does.
 //     The panels are staged again for every evaluation (from L2 once m exceeds a panel).  A finished start is frozen: its
 //     rows are not evaluated, nothing of it is written again, its lanes only take part in the barriers.
 //   * path_eval_kernel (with a projection): one evaluation of the library-side loop, the same device function over the ns
@@ -150,53 +151,6 @@ __global__ __launch_bounds__(256) void path_eval_kernel(PathEvalArgs e, int use_
   path_eval<KS4, DT>(e, L, blockIdx.x * PR_ROWS + (tid >> 6) * 16, use_status != 0);
 }
 
-// One step of the rule for start i after an evaluation, on the arrays of the library-side loop and by the serial functions of
-// refine_step.h (what refine_step_kernel does for a start).  first: (ay, gy) is the evaluation at the clipped start in y.
-// Returns whether the start goes on; y then holds its next trial point.  A frozen start is left as it is.
-__device__ __forceinline__ bool path_step(const RefineStepArgs& a, int i, bool first) {
-  const int D = a.D;
-  const int64_t rec = 2 * D + 3;
-  double *const x = a.x + (int64_t)i * D, *const g = a.g + (int64_t)i * D, *const y = a.y + (int64_t)i * D;
-  const double* const gy = a.gy + (int64_t)i * D;
-  RefineStart st;
-  bool acc = true;
-  double alpha = 0.0;
-  int at = 0;
-  if (!first) {
-    st.status = a.status[i];
-    if (st.status != REFINE_ACTIVE) return false;
-  }
-  const double ay = a.ay[i];
-  if (first) {
-    for (int k = 0; k < D; ++k) {
-      x[k] = y[k];
-      g[k] = gy[k];
-    }
-    refine_begin(D, x, g, ay, a.lower, a.upper, a.scale, a.o, st, y);
-  } else {
-    st.a = a.a[i]; st.alpha = a.alpha[i]; st.evals = a.evals[i]; st.accepted = a.accepted[i];
-    alpha = st.alpha;
-    at = st.evals;
-    if (a.trace) {
-      double* const tr = a.trace + ((int64_t)i * a.o.max_evals + at) * rec;
-      for (int k = 0; k < D; ++k) tr[k] = y[k];
-    }
-    acc = refine_advance(D, x, g, y, gy, ay, a.lower, a.upper, a.scale, a.o, st);
-  }
-  if (a.trace) {
-    double* const tr = a.trace + ((int64_t)i * a.o.max_evals + at) * rec;
-    for (int k = 0; k < D; ++k) {
-      if (first) tr[k] = x[k];
-      tr[D + k] = gy[k];
-    }
-    tr[2 * D] = ay;
-    tr[2 * D + 1] = alpha;
-    tr[2 * D + 2] = acc ? 1.0 : 0.0;
-  }
-  a.a[i] = st.a; a.alpha[i] = st.alpha; a.evals[i] = st.evals; a.accepted[i] = st.accepted; a.status[i] = st.status;
-  return st.status == REFINE_ACTIVE;
-}
-
 // e.pts / e.val / e.grad / e.status are st.y / st.ay / st.gy / st.status (e.ldg = e.d = st.D): an evaluation, a barrier (the
 // workgroup's own stores are visible to it then), the step of the workgroup's 64 starts by its first wavefront, and the
 // vote.  The trip count is the same for the whole workgroup.
@@ -214,7 +168,7 @@ __global__ __launch_bounds__(256) void path_refine_kernel(PathEvalArgs e, Refine
     path_eval<KS4, DT>(e, L, r0 + (tid >> 6) * 16, !first);
     __syncthreads();
     int more = 0;
-    if (tid < PR_ROWS && r0 + tid < st.ns) more = path_step(st, r0 + tid, first) ? 1 : 0;
+    if (tid < PR_ROWS && r0 + tid < st.ns) more = refine_step_start<false>(st, r0 + tid, first) ? 1 : 0;
     first = false;
     if (!__syncthreads_or(more)) break;
   }

@@ -8,8 +8,8 @@
 //     point only, and the sums and maxima of the rule are butterflies over a start's 16 lanes: a start's result does not
 //     depend on what shares its wavefront or workgroup.  No atomics.
 //   * refine_step_kernel (every other shape): the step between two evaluations of the library-side loop, one start per
-//     thread on [ns][D] arrays, calling the serial functions of refine_step.h.  One workgroup counts the starts that go on
-//     through LDS and writes the count where the host reads it.
+//     thread on [ns][D] arrays: refine_step_start of refine_step.h, which path_refine_kernel (path_refine.hip) and the host
+//     check call too.  One workgroup counts the starts that go on through LDS and writes the count where the host reads it.
 #include <type_traits>
 
 #include "small_pg.h"
@@ -38,47 +38,9 @@ void small_refine_attrs() {
 
 __global__ __launch_bounds__(256) void refine_step_kernel(RefineStepArgs a) {
   __shared__ int cnt[256];
-  const int tid = threadIdx.x, D = a.D;
-  const int64_t rec = 2 * D + 3;
+  const int tid = threadIdx.x;
   int mine = 0;
-  for (int i = tid; i < a.ns; i += 256) {
-    double *const x = a.x + (int64_t)i * D, *const g = a.g + (int64_t)i * D, *const y = a.y + (int64_t)i * D;
-    const double* const gy = a.gy + (int64_t)i * D;
-    const double ay = a.ay[i];
-    RefineStart st;
-    bool acc = true;
-    double alpha = 0.0;
-    int at = 0;
-    if (a.first) {
-      for (int k = 0; k < D; ++k) {  // y holds the clipped start
-        x[k] = y[k];
-        g[k] = gy[k];
-      }
-      refine_begin(D, x, g, ay, a.lower, a.upper, a.scale, a.o, st, y);
-    } else {
-      st.a = a.a[i]; st.alpha = a.alpha[i]; st.evals = a.evals[i]; st.accepted = a.accepted[i]; st.status = a.status[i];
-      if (st.status != REFINE_ACTIVE) continue;  // frozen
-      alpha = st.alpha;
-      at = st.evals;
-      if (a.trace) {
-        double* const tr = a.trace + ((int64_t)i * a.o.max_evals + at) * rec;
-        for (int k = 0; k < D; ++k) tr[k] = y[k];
-      }
-      acc = refine_advance(D, x, g, y, gy, ay, a.lower, a.upper, a.scale, a.o, st);
-    }
-    if (a.trace) {
-      double* const tr = a.trace + ((int64_t)i * a.o.max_evals + at) * rec;
-      for (int k = 0; k < D; ++k) {
-        if (a.first) tr[k] = x[k];
-        tr[D + k] = gy[k];
-      }
-      tr[2 * D] = ay;
-      tr[2 * D + 1] = alpha;
-      tr[2 * D + 2] = acc ? 1.0 : 0.0;
-    }
-    a.a[i] = st.a; a.alpha[i] = st.alpha; a.evals[i] = st.evals; a.accepted[i] = st.accepted; a.status[i] = st.status;
-    if (st.status == REFINE_ACTIVE) ++mine;
-  }
+  for (int i = tid; i < a.ns; i += 256) mine += refine_step_start<true>(a, i, a.first != 0) ? 1 : 0;
   cnt[tid] = mine;
   __syncthreads();
   for (int off = 128; off >= 1; off >>= 1) {

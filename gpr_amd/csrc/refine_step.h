@@ -1,8 +1,9 @@
 // The step rule of gprhip_acquire_refine: projected gradient ascent with Armijo backtracking on one start inside a box
 // (include/gprhip.h has the contract).  One copy for the host and the device: the persistent kernel of refine.hip (a start's
-// components spread over 16 lanes) and refine_step_kernel (one start per thread) call these functions, and so does
-// tests/cpp/refine_step_check.cpp on analytic objectives.  The objective is any "larger is better" function with a gradient:
-// nothing here knows of the acquisition criteria (a drawn sample path would do as well).
+// components spread over 16 lanes) calls the arithmetic; refine_step_kernel (one start per thread), path_refine_kernel (one
+// lane per start) and tests/cpp/refine_step_check.cpp on analytic objectives call refine_step_start, the step of one start on
+// [ns][D] arrays.  The objective is any "larger is better" function with a gradient: nothing here knows of the acquisition
+// criteria (gprhip_sample_paths_refine climbs drawn sample paths with it).
 //
 // Per start, with w_k = upper_k - lower_k:
 //   1. x = clip(start); (a, g) the objective and its gradient at x; evals = 1.  a NaN: status NAN.
@@ -13,9 +14,11 @@
 //      NaN): accept -- x, a, g = y, a_y, g_y, ++accepted, dir again (all zero: CONVERGED), alpha *= grow;  else alpha *= shrink.
 //   4. MAX_EVALS when the evaluations run out.
 // The functions of the first group are the rule's arithmetic, component by component; RefineStart and the three functions of
-// the second group are the rule for a start whose components one thread holds.
+// the second group are the rule for a start whose components one thread holds; RefineStepArgs and refine_step_start are that
+// rule driven on the arrays that hold the starts of a call between two evaluations.
 #pragma once
 #include <math.h>
+#include <stdint.h>
 
 #ifndef GPRHIP_REFINE_FN
 #define GPRHIP_REFINE_FN __host__ __device__ __forceinline__
@@ -136,6 +139,77 @@ GPRHIP_REFINE_FN bool refine_advance(int D, double* x, double* g, double* y, con
   }
   refine_propose(D, x, g, lo, hi, scale, o, st, y);
   return acc;
+}
+
+// ---- the starts of a call as [ns][D] arrays (device memory on the device): the state between two evaluations
+// first: (ay, gy) is the evaluation at the clipped starts in y (x, g and the per-start state are initialised from it), else at
+// the trial points y.  y receives the next trial points.  The trace is [ns][max_evals][2 D + 3] records (y, g_y, a_y, alpha,
+// accepted), one per evaluation.  `first` and `active` belong to refine_step_kernel: *active (pinned host memory,
+// device-visible) receives the number of starts that go on.
+struct RefineStepArgs {
+  int ns, D, first;
+  const double *lower, *upper, *scale;  // [D]; scale may be null
+  RefineOpts o;
+  double *x, *g, *y;                    // [ns][D]
+  const double *gy, *ay;                // [ns][D], [ns]
+  double *a, *alpha;                    // [ns]
+  int *evals, *accepted, *status;       // [ns]
+  double* trace;                        // or null
+  int* active;
+};
+
+// One step of the rule for start i after an evaluation: its state is loaded from the arrays, refine_begin or refine_advance
+// runs on it, the trace record of the evaluation is written and the state is stored back.  Returns whether the start goes on;
+// y then holds its next trial point.  A frozen start (status not REFINE_ACTIVE after the first evaluation) is left untouched.
+// AY_LATE: where the load of a_y stands -- straight after the status read, or inside each branch behind the other loads.  The
+// results are the same; the compiler's register allocation is not (profiles/refine_regs.txt, profiles/path_refine_regs.txt):
+// refine_step_kernel takes true, path_refine_kernel false.
+template <bool AY_LATE>
+GPRHIP_REFINE_FN bool refine_step_start(const RefineStepArgs& a, int i, bool first) {
+  const int D = a.D;
+  const int64_t rec = 2 * D + 3;
+  double *const x = a.x + (int64_t)i * D, *const g = a.g + (int64_t)i * D, *const y = a.y + (int64_t)i * D;
+  const double* const gy = a.gy + (int64_t)i * D;
+  RefineStart st;
+  bool acc = true;
+  double alpha = 0.0;
+  int at = 0;
+  if (!first) {  // the status alone first: a frozen start costs one load
+    st.status = a.status[i];
+    if (st.status != REFINE_ACTIVE) return false;
+  }
+  double ay;  // (no initialiser: path_refine_kernel keeps the instructions it had)
+  if (!AY_LATE) ay = a.ay[i];
+  if (first) {
+    if (AY_LATE) ay = a.ay[i];
+    for (int k = 0; k < D; ++k) {  // y holds the clipped start
+      x[k] = y[k];
+      g[k] = gy[k];
+    }
+    refine_begin(D, x, g, ay, a.lower, a.upper, a.scale, a.o, st, y);
+  } else {
+    st.a = a.a[i]; st.alpha = a.alpha[i]; st.evals = a.evals[i]; st.accepted = a.accepted[i];
+    if (AY_LATE) ay = a.ay[i];
+    alpha = st.alpha;
+    at = st.evals;
+    if (a.trace) {
+      double* const tr = a.trace + ((int64_t)i * a.o.max_evals + at) * rec;
+      for (int k = 0; k < D; ++k) tr[k] = y[k];
+    }
+    acc = refine_advance(D, x, g, y, gy, ay, a.lower, a.upper, a.scale, a.o, st);
+  }
+  if (a.trace) {
+    double* const tr = a.trace + ((int64_t)i * a.o.max_evals + at) * rec;
+    for (int k = 0; k < D; ++k) {
+      if (first) tr[k] = x[k];
+      tr[D + k] = gy[k];
+    }
+    tr[2 * D] = ay;
+    tr[2 * D + 1] = alpha;
+    tr[2 * D + 2] = acc ? 1.0 : 0.0;
+  }
+  a.a[i] = st.a; a.alpha[i] = st.alpha; a.evals[i] = st.evals; a.accepted[i] = st.accepted; a.status[i] = st.status;
+  return st.status == REFINE_ACTIVE;
 }
 
 }  // namespace gprhip

@@ -4,7 +4,7 @@ device pointers over the same ns points (the parent commit's kernels; the yardst
 timed INTERLEAVED in one process on one device: host wall time of the blocking calls, median of REPS after two warm-ups.
 Shapes as tools/bench_refine.py: n = 2000 / m = 50 (d = 3), n = 10 000 / m = 256 and n = 100 000 / m = 2048 (d = 8), each with
 64 and 1024 starts.  `evals` of a refine call is its largest per-start evaluation count.  Then the HIP-event stage times
-(timing level 2) of one refine call.  Every line of the output file is written by this tool.
+(timing level 2) of one refine call.  The table is written by this tool; a comparison of runs may follow it as comment lines.
     usage (GPU box, repo root): timeout 900 python3 tools/bench_path_refine.py [--out profiles/path_refine_cost.txt] [--skip-big]
 """
 import os
@@ -26,9 +26,9 @@ shapes = [("n=2000 m=50", 2000, 50, 3), ("n=10000 m=256", 10000, 256, 8)]
 if "--skip-big" not in sys.argv:
     shapes += [("n=100000 m=2048", 100000, 2048, 8)]
 lines = ["# tools/bench_path_refine.py: sample_paths_refine (%d draws, max_evals %d) vs evals x predict_input_grad (means + dmeans)," % (ND, MAX_EVALS),
-         "# device pointers, interleaved, host wall time in ms (median of %d after 2 warm-ups); per eval: the call over its" % REPS,
+         "# device pointers, interleaved, host wall time in ms (median of %d after 2 warm-ups, and the least and the largest of them for the refine call); per eval: the call over its" % REPS,
          "# evaluations; stages: HIP events (timing level 2) of one refine call",
-         "%-16s %6s %6s %10s %12s %10s %12s %7s   %s" % ("shape", "ns", "evals", "refine", "refine/eval", "loop", "grad/call", "ratio",
+         "%-16s %6s %6s %10s %12s %10s %12s %7s %15s   %s" % ("shape", "ns", "evals", "refine", "refine/eval", "loop", "grad/call", "ratio", "refine min-max",
                                                         "stages (ms)")]
 dev = "cuda:0"
 for name, n, m, d in shapes:
@@ -69,12 +69,13 @@ for name, n, m, d in shapes:
                 f()
                 t.append(time.perf_counter() - t0)
         tr, tl = (1e3 * float(np.median(t[2:])) for t in times)
+        spread = "%.3f-%.3f" % (1e3 * min(times[0][2:]), 1e3 * max(times[0][2:]))
         p.set_timing(2)
         refine()
         stg = p.last_timings()
         p.set_timing(0)
         stages = "  ".join("%s %.3f" % (k, v) for k, v in stg.items() if k.startswith(("sp_", "prf_", "rf_")))
-        lines.append("%-16s %6d %6d %10.3f %12.4f %10.3f %12.4f %7.2f   %s" % (name, ns, evals, tr, tr / evals, tl, tl / evals, tr / tl, stages))
+        lines.append("%-16s %6d %6d %10.3f %12.4f %10.3f %12.4f %7.2f %15s   %s" % (name, ns, evals, tr, tr / evals, tl, tl / evals, tr / tl, spread, stages))
         print(lines[-1], flush=True)
         del outs, st
     p.close()

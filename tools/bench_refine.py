@@ -5,7 +5,7 @@ in one process on one device: host wall time of the blocking calls, median of RE
 (the library-side loop).  `evals` of a refine call is its largest per-start evaluation count -- the number of evaluations the
 loop made; the yardstick runs that many acquire calls (the parent commit's kernels but for PI's coefficients where phi is
 subnormal, acq_math.h; log EI, timed here, is instruction for instruction the parent's).  Then the HIP-event stage times
-(timing level 2) of one refine call.  Every line of the output file is written by this tool.
+(timing level 2) of one refine call.  The table is written by this tool; a comparison of runs may follow it as comment lines.
     usage (GPU box, repo root): timeout 900 python3 tools/bench_refine.py [--out profiles/refine_cost.txt] [--skip-big]
 """
 import os
@@ -27,9 +27,9 @@ shapes = [("n=2000 m=50", 2000, 50, 3, 64), ("n=2000 m=50", 2000, 50, 3, 1024), 
 if "--skip-big" not in sys.argv:
     shapes += [("n=100000 m=2048", 100000, 2048, 8, 64)]
 lines = ["# tools/bench_refine.py: acquire_refine (log EI, max_evals %d) vs evals x acquire, device pointers, interleaved, host wall" % MAX_EVALS,
-         "# time in ms (median of %d after 2 warm-ups); per eval: the call over its evaluations; stages: HIP events (timing level 2) of" % REPS,
+         "# time in ms (median of %d after 2 warm-ups, and the least and the largest of them for the refine call); per eval: the call over its evaluations; stages: HIP events (timing level 2) of" % REPS,
          "# one refine call, summed over its evaluations",
-         "%-16s %6s %6s %10s %12s %10s %12s %7s   %s" % ("shape", "ns", "evals", "refine", "refine/eval", "loop", "acquire/call", "ratio",
+         "%-16s %6s %6s %10s %12s %10s %12s %7s %15s   %s" % ("shape", "ns", "evals", "refine", "refine/eval", "loop", "acquire/call", "ratio", "refine min-max",
                                                         "stages (ms)")]
 dev = "cuda:0"
 for name, n, m, d, ns in shapes:
@@ -69,12 +69,13 @@ for name, n, m, d, ns in shapes:
             f()
             t.append(time.perf_counter() - t0)
     tr, tl = (1e3 * float(np.median(t[2:])) for t in times)
+    spread = "%.3f-%.3f" % (1e3 * min(times[0][2:]), 1e3 * max(times[0][2:]))
     p.set_timing(2)
     refine()
     stg = p.last_timings()
     p.set_timing(0)
     stages = "  ".join("%s %.3f" % (k, v) for k, v in stg.items() if k.startswith(("pg_", "rf_")))
-    lines.append("%-16s %6d %6d %10.3f %12.4f %10.3f %12.4f %7.2f   %s" % (name, ns, evals, tr, tr / evals, tl, tl / evals, tr / tl, stages))
+    lines.append("%-16s %6d %6d %10.3f %12.4f %10.3f %12.4f %7.2f %15s   %s" % (name, ns, evals, tr, tr / evals, tl, tl / evals, tr / tl, spread, stages))
     print(lines[-1], flush=True)
     p.close()
     del outs, st, X, y, Z
