@@ -84,6 +84,12 @@ external device_count : unit -> int = "gprhip_ml_device_count"
 external version : unit -> string = "gprhip_ml_version"
 external condition : problem -> float * float = "gprhip_ml_condition"
 external debug_fetch : problem -> string -> vec -> unit = "gprhip_ml_debug_fetch"
+(* new observations folded into the predictor state without a refit (gprhip_observe, gprhip_posterior_save / _restore):
+   points D x k (k <= 64) -> targets (None: a state without targets) -> the log density of the new targets given the old *)
+external observe : problem -> mat -> vec option -> float = "gprhip_ml_observe"
+external posterior_save : problem -> unit = "gprhip_ml_posterior_save"
+external posterior_restore : problem -> unit = "gprhip_ml_posterior_restore"
+external observed_count : problem -> int = "gprhip_ml_observed_count"
 
 (* single-process, multi-device (include/gprhip.h: gprhip_ctx_*, gprhip_sharded_*): the path the functors below take *)
 type ctx (* custom block; finaliser calls gprhip_ctx_destroy (deferred by the library while sharded problems live) *)
@@ -673,6 +679,38 @@ module Make_variant
         res
 
       let sample ?rng t = Mat.col (samples ?rng t ~n:1) 1
+    end
+
+    (* New observations folded into the device state of a trained model or a model without a refit (an extension beyond the
+       reference's signature, whose values are immutable).  MUTATING: every posterior function on that value reads the
+       conditioned state afterwards; its targets, its evidence and the resident training set are not touched, and the next
+       evaluation on the shared device inputs forgets the observations and drops the saved slot.  The m x m state is
+       replicated over the shards of the context, so every shard's problem takes the same update. *)
+    module Observe = struct
+      let problems (dev : device_inputs) =
+        List.init (ctx_ndev (Lazy.force context)) (fun i -> sharded_problem dev.sp i)
+
+      let fold dev (inputs : Inputs.t) targets =
+        List.fold_left (fun _ p -> observe p inputs.Inputs.points targets) 0. (problems dev)
+
+      (* the joint log density of the new targets given everything before them *)
+      let observe (trained : Trained.t) (inputs : Inputs.t) ~targets =
+        same_inducing trained.Trained.model.Model.inputs.Inputs.inducing.Inducing.points
+          inputs.Inputs.inducing.Inducing.points "Observe.observe";
+        Trained.ensure_state trained;
+        fold (Lazy.force trained.Trained.model.Model.inputs.Inputs.dev) inputs (Some targets)
+
+      (* a model has no targets: the factors alone, and the model's share of the evidence *)
+      let observe_model (model : Model.t) (inputs : Inputs.t) =
+        same_inducing model.Model.inputs.Inputs.inducing.Inducing.points inputs.Inputs.inducing.Inducing.points
+          "Observe.observe_model";
+        Model.ensure_state model;
+        fold (Lazy.force model.Model.inputs.Inputs.dev) inputs None
+
+      (* (no state is made here: after another evaluation took the device, restore is the library's state error) *)
+      let save (model : Model.t) = List.iter posterior_save (problems (Lazy.force model.Model.inputs.Inputs.dev))
+      let restore (model : Model.t) = List.iter posterior_restore (problems (Lazy.force model.Model.inputs.Inputs.dev))
+      let count (model : Model.t) = observed_count (Lazy.force model.Model.inputs.Inputs.dev).first
     end
 
     (* Draws of the posterior as functions (an extension beyond the reference's signature): a sampler keeps its m x n normal

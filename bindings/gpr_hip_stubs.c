@@ -644,6 +644,46 @@ CAMLprim value gprhip_ml_condition(value prob) {
   CAMLreturn(res);
 }
 
+/* external observe : problem -> mat -> vec option -> float
+ *   folds the k columns of the D x k points (k <= 64) into the predictor state without a refit (gprhip_observe); targets: one per
+ *   point, None for a state without targets.  Returns the joint log density of the new targets given everything before them. */
+CAMLprim value gprhip_ml_observe(value prob, value points, value targets) {
+  CAMLparam3(prob, points, targets);
+  struct caml_ba_array* ba = Caml_ba_array_val(points);
+  gprhip_problem* p = Problem_val(prob);
+  const double* x = (const double*)ba->data;
+  const double* y = opt_data(targets);
+  int64_t ld = ba->dim[0];
+  int k = (int)ba->dim[1], status;
+  double dl = 0.0;
+  if (Is_block(targets) && Caml_ba_array_val(Field(targets, 0))->dim[0] != ba->dim[1])
+    caml_invalid_argument("Gpr_hip.observe: one target per new point");
+  caml_release_runtime_system();
+  status = gprhip_observe(p, x, ld, y, k, &dl, 0);
+  caml_acquire_runtime_system();
+  check(status);
+  CAMLreturn(caml_copy_double(dl));
+}
+
+/* external posterior_save : problem -> unit      external posterior_restore : problem -> unit */
+CAMLprim value gprhip_ml_posterior_save(value prob) {
+  CAMLparam1(prob);
+  check(gprhip_posterior_save(Problem_val(prob)));
+  CAMLreturn(Val_unit);
+}
+
+CAMLprim value gprhip_ml_posterior_restore(value prob) {
+  CAMLparam1(prob);
+  check(gprhip_posterior_restore(Problem_val(prob)));
+  CAMLreturn(Val_unit);
+}
+
+/* external observed_count : problem -> int */
+CAMLprim value gprhip_ml_observed_count(value prob) {
+  CAMLparam1(prob);
+  CAMLreturn(Val_long((long)gprhip_observed_count(Problem_val(prob))));
+}
+
 /* external debug_fetch : problem -> string -> vec -> unit      intermediates of the last evaluation (parity tests) */
 CAMLprim value gprhip_ml_debug_fetch(value prob, value name, value out) {
   CAMLparam3(prob, name, out);

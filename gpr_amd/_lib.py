@@ -116,6 +116,7 @@ MAX_TOP_K = 64    # GPRHIP_MAX_TOP_K
 MAX_DRAWS = 64    # GPRHIP_MAX_DRAWS
 MAX_TARGETS = 16  # GPRHIP_MAX_TARGETS
 MAX_BATCH = 64    # GPRHIP_MAX_BATCH
+MAX_OBSERVE = 64  # GPRHIP_MAX_OBSERVE
 
 # name -> (restype, argtypes); the single source of truth for tests/test_abi.py as well
 _dp = C.POINTER(C.c_double)
@@ -165,6 +166,10 @@ SIGNATURES = {
                                      C.c_int64, _dp]),
     "gprhip_co_variance_coeffs": (C.c_int, [_vp, _dp, _dp]),
     "gprhip_load_predictor": (C.c_int, [_vp, C.POINTER(Hypers), _dp, _dp, _dp]),
+    "gprhip_observe": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int, _dp, C.c_int]),
+    "gprhip_posterior_save": (C.c_int, [_vp]),
+    "gprhip_posterior_restore": (C.c_int, [_vp]),
+    "gprhip_observed_count": (C.c_int64, [_vp]),
     "gprhip_condition": (C.c_int, [_vp, _dp, _dp]),
     "gprhip_debug_fetch": (C.c_int, [_vp, C.c_char_p, _dp, C.c_int64]),
     "gprhip_last_timings": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),

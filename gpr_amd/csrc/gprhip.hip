@@ -299,6 +299,17 @@ struct gprhip_problem {
   char* sp_scratch = nullptr;
   int64_t sp_scratch_bytes = 0;
   double *sp_out = nullptr, *sp_host = nullptr;
+  // gprhip_observe: have_b -- bvec holds b = R~ (U t) of the current model state (every evaluation leaves it; a loaded predictor
+  // forms it once, at the first call); n_observed -- observations folded in since the last evaluation or gprhip_load_predictor;
+  // obs_buf -- the scratch of a call (obs_len doubles); post_slot -- gprhip_posterior_save's copy [R~ | R~^-1 | b | t~ | t],
+  // released by an evaluation and by gprhip_load_predictor
+  bool have_b = false;
+  int64_t n_observed = 0;
+  double* obs_buf = nullptr;
+  int64_t obs_len = 0;
+  double* post_slot = nullptr;
+  int64_t slot_observed = 0;
+  bool slot_have_b = false;
   bool use_small() const {
     return !multi && !xg_engine && small_path && !f32 && !engine_steps && small_path_fits(m, mp, d, has_proj() ? D : 0, n, has_ms());
   }
@@ -359,6 +370,17 @@ template <> const float* inv_rfull<float>(const gprhip_problem* p) { return p->r
 
 void need_trustworthy_coeffs(gprhip_problem* p, const char* who);
 void need_factors(gprhip_problem* p, const char* who);
+
+template <typename T>
+void release_buf(gprhip_problem* p, T*& q);
+
+// a new model state (an evaluation, gprhip_load_predictor): the observations folded into the old one and the saved
+// posterior slot of gprhip_posterior_save belong to that old state
+void forget_observations(gprhip_problem* p) {
+  p->have_b = false;
+  p->n_observed = 0;
+  release_buf(p, p->post_slot);
+}
 
 void tstart(gprhip_problem* p, const char* name) {
   if (!p->timer.on) return;
@@ -1121,6 +1143,7 @@ void do_pass1(gprhip_problem* p, const gprhip_hypers* h, int want_grad, int64_t 
   p->cond_km = -1.0;
   p->pg_m_valid = false;
   p->sp_ns_last = 0;
+  forget_observations(p);
   upload_hypers(p, h);
   p->want_grad = want_grad;
   p->n_total = n_total;
@@ -1594,6 +1617,7 @@ void do_finish_collect(gprhip_problem* p, gprhip_result* res, double* grad, doub
   }
   p->have_model = true;
   p->have_factors = true;
+  p->have_b = true;  // (pass2_b_chol left b = R~^-T c~ in bvec)
   if (light) return;
   const bool mo = p->h.model_only != 0;
   const double sum_log_s = ha1tail[A1_SUMLOGS], sum_isr = ha1tail[A1_ISR], sum_isy2 = ha1tail[A1_ISY2];
@@ -1762,6 +1786,7 @@ void batch_stage_lane(gprhip_batch* b, int j, const gprhip_hypers* h, int want_g
   l->cond_km = -1.0;
   l->pg_m_valid = false;
   l->sp_ns_last = 0;
+  forget_observations(l);
   l->have_v = l->have_k = l->small_k_valid = false;
   stage_hypers(l, h);
   l->want_grad = want_grad;
@@ -2997,6 +3022,7 @@ void do_load_predictor(gprhip_problem* p, const gprhip_hypers* h, const double* 
   p->cond_km = -1.0;
   p->pg_m_valid = false;
   p->sp_ns_last = 0;
+  forget_observations(p);
   upload_hypers(p, h);
   std::vector<double> t(mp, 0.0);
   if (coeffs) std::memcpy(t.data(), coeffs, (size_t)m * sizeof(double));
@@ -3027,6 +3053,206 @@ void do_load_predictor(gprhip_problem* p, const gprhip_hypers* h, const double* 
   p->stage = 0;
   p->have_model = true;
   p->h.model_only = coeffs ? 0 : 1;
+}
+
+// ---- gprhip_observe / gprhip_posterior_save / gprhip_posterior_restore
+// A training point enters the FITC posterior through its row v = K_xm U^-1 of V, s = sf2 - |v|^2 + sigma2 and y alone
+// (lib/fitc_gp.ml:151-182): with w = v / sqrt(s), eta = y / sqrt(s), B~' = B~ + sum w w^T and c~' = c~ + sum w eta, so
+// [R~' | b'] is the triangular factor of [R~ | b] stacked on [W | eta].
+void need_observe_state(gprhip_problem* p, const char* fn) {
+  need_posterior_state(p, fn, "work from", true, true, false, "");
+  if (p->multi_state) {
+    set_error(std::string(fn) + ": the last evaluation was gprhip_eval_targets (several target vectors); the single-target "
+              "state it needs comes from gprhip_eval");
+    throw HipFail{ST_STATE};
+  }
+}
+
+// b = R~ (U t) of a predictor that was loaded (an evaluation leaves b itself, which is never re-made from t: the product
+// cancels when K_m is ill-conditioned)
+void ensure_b(gprhip_problem* p, double* tmp) {
+  if (p->have_b || p->h.model_only) return;
+  launch_triu_matvec(p->umat, p->mp, p->tvec, tmp, 0, p->stream);
+  launch_triu_matvec(p->bmat, p->mp, tmp, p->bvec, 0, p->stream);
+  p->have_b = true;
+}
+
+void do_observe(gprhip_problem* p, const double* inputs, int64_t ld, const double* targets, int k, double* dlog_evidence,
+                int on_device) {
+  const char* const fn = "gprhip_observe";
+  const int D = p->D, m = p->m, mp = p->mp;
+  GPR_HIP(hipSetDevice(p->device));
+  hipStream_t s = p->stream;
+  // finite inputs and targets (device buffers are read back once)
+  {
+    std::vector<double> hx, hy;
+    const double* x = inputs;
+    const double* y = targets;
+    int64_t ldx = ld;
+    if (on_device) {
+      hx.resize((size_t)k * D);
+      GPR_HIP(hipMemcpyAsync(hx.data(), inputs, hx.size() * 8, hipMemcpyDeviceToHost, s));
+      if (targets) {
+        hy.resize(k);
+        GPR_HIP(hipMemcpyAsync(hy.data(), targets, (size_t)k * 8, hipMemcpyDeviceToHost, s));
+        y = hy.data();
+      }
+      GPR_HIP(hipStreamSynchronize(s));
+      x = hx.data();
+      ldx = D;
+    }
+    bool finite = true;
+    for (int i = 0; i < k; ++i) {
+      for (int b = 0; b < D; ++b) finite = finite && std::isfinite(x[i * ldx + b]);
+      if (y) finite = finite && std::isfinite(y[i]);
+    }
+    if (!finite) {
+      set_error(std::string(fn) + ": a non-finite input or target");
+      throw HipFail{ST_BAD_ARG};
+    }
+  }
+  // buffers first: a refusal for memory leaves everything as it was
+  const int64_t need = (int64_t)OBS_MAX_ROWS * mp + 4 * OBS_MAX_ROWS + (int64_t)TILE * 64 + 2 * TILE + 2 * (int64_t)mp + 2;
+  if (p->obs_len < need) {
+    GPR_HIP(hipStreamSynchronize(s));
+    size_t free_b = 0, total_b = 0;
+    GPR_HIP(hipMemGetInfo(&free_b, &total_b));
+    if ((uint64_t)need * 8 > (uint64_t)free_b) {
+      set_error(std::string(fn) + ": not enough free device memory for the update's scratch");
+      throw HipFail{ST_OOM};
+    }
+    grow_buf(p, p->obs_buf, p->obs_len, need);
+  }
+  double* const W = p->obs_buf;
+  double* const eta = W + (int64_t)OBS_MAX_ROWS * mp;
+  double* const rs = eta + OBS_MAX_ROWS;
+  double* const ydev = rs + 2 * OBS_MAX_ROWS;
+  double* const ubuf = ydev + OBS_MAX_ROWS;
+  double* const vb = ubuf + (int64_t)TILE * 64;
+  double* const ldr = vb + 2 * TILE;
+  double* const tmpv = ldr + mp;
+  double* const out = tmpv + mp;
+  const ChunkPlan plan = chunk_plan(p, k, true);
+  chunk_alloc(p, plan);
+  double* const bufA = static_cast<double*>(plan.chunk > p->chunk ? p->predA : p->bufA);
+  double* const bufB = static_cast<double*>(plan.chunk > p->chunk ? p->predB : p->bufB);
+  // rows: the k points as one padded tile through the launches gprhip_predict uses for its variance, then W, eta, r and s
+  walk_chunks(p, plan.chunk, inputs, ld, k, on_device, [&](int64_t, int rows, int rows_p, const double*, const double* pts) {
+    tstart(p, "obs_rows");
+    launch_cov_cross<double>(p->cp, pts, rows, rows_p, p->Z, m, mp, p->d, bufA, s);
+    GemmArgs g;  // trsm ~side:`R chol_km
+    g.A = bufA; g.lda = mp; g.B = p->uinv; g.ldb = mp; g.C = bufB; g.ldc = mp;
+    g.M = rows_p; g.N = mp; g.K = mp; g.tri = TRI_KHI_BN;
+    launch_gemm(OP_NN, g, s);
+    launch_row_sumsq_dot<double>(bufB, nullptr, rows, mp, p->prow, nullptr, s);
+    if (targets)
+      GPR_HIP(hipMemcpyAsync(ydev, targets, (size_t)k * 8, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    ObsRowsArgs a;
+    a.V = bufB; a.sumsq = p->prow; a.y = targets ? ydev : nullptr; a.k = k; a.m = m; a.mp = mp;
+    a.sf2 = p->cp.sf2; a.sigma2 = p->h.sigma2; a.W = W; a.eta = eta; a.rs = rs;
+    launch_obs_rows(a, s);
+    tstop(p);
+  });
+  // s comes back before anything of the state is written
+  double hrs[2 * OBS_MAX_ROWS];
+  GPR_HIP(hipMemcpyAsync(hrs, rs, sizeof hrs, hipMemcpyDeviceToHost, s));
+  GPR_HIP(hipStreamSynchronize(s));
+  for (int i = 0; i < k; ++i)
+    if (!(hrs[OBS_MAX_ROWS + i] > 0.0)) {
+      char buf[200];
+      snprintf(buf, sizeof buf, "%s: s = sf2 - |K_xm U^-1|^2 + sigma2 = %.3g of new point %d is not positive", fn,
+               hrs[OBS_MAX_ROWS + i], i + 1);
+      set_error(buf);
+      throw HipFail{ST_NOT_POSDEF};
+    }
+  ensure_b(p, tmpv);
+  tstart(p, "obs_update");
+  ObsUpdateArgs u;
+  u.R = p->bmat; u.m = m; u.mp = mp; u.k = k; u.W = W; u.b = targets ? p->bvec : nullptr; u.eta = eta;
+  u.u = ubuf; u.vb = vb; u.ldr = ldr; u.out = out;
+  launch_obs_update(u, s);
+  tstop(p);
+  tstart(p, "obs_inverse");
+  trtri_of_factor(p, p->bmat, p->rinv);
+  tstop(p);
+  tstart(p, "obs_vectors");
+  if (targets) {
+    launch_triu_matvec(p->rinv, mp, p->bvec, p->ttil, 0, s);  // t~' = R~'^-1 b'
+    launch_triu_matvec(p->uinv, mp, p->ttil, p->tvec, 0, s);  // t' = U^-1 t~'
+  }
+  tstop(p);
+  double hout[2];
+  GPR_HIP(hipMemcpyAsync(hout, out, sizeof hout, hipMemcpyDeviceToHost, s));
+  GPR_HIP(hipStreamSynchronize(s));
+  p->pg_m_valid = false;
+  p->sp_ns_last = 0;
+  p->n_observed += k;
+  if (p->timer.on) tcollect(p);
+  if (dlog_evidence) {
+    double sum_log_s = 0.0, sum_isr = 0.0;
+    for (int i = 0; i < k; ++i) {
+      sum_log_s += std::log(hrs[OBS_MAX_ROWS + i]);
+      sum_isr += hrs[i] / hrs[OBS_MAX_ROWS + i];
+    }
+    double dl = -0.5 * (2.0 * hout[0] + sum_log_s + (double)k * LOG_2PI);
+    if (p->h.variational) dl += -0.5 * sum_isr;
+    if (targets) dl += -0.5 * hout[1];
+    *dlog_evidence = dl;
+  }
+}
+
+void do_posterior_save(gprhip_problem* p) {
+  need_observe_state(p, "gprhip_posterior_save");
+  GPR_HIP(hipSetDevice(p->device));
+  hipStream_t s = p->stream;
+  const int64_t mp = p->mp, mm = mp * mp, len = 2 * mm + 3 * mp;
+  if (!p->post_slot) {
+    GPR_HIP(hipStreamSynchronize(s));
+    size_t free_b = 0, total_b = 0;
+    GPR_HIP(hipMemGetInfo(&free_b, &total_b));
+    if ((uint64_t)len * 8 > (uint64_t)free_b) {
+      char buf[200];
+      snprintf(buf, sizeof buf, "gprhip_posterior_save: the slot needs %.3f GB on device %d and %.3f GB are free", len * 8 / 1e9,
+               p->device, free_b / 1e9);
+      set_error(buf);
+      throw HipFail{ST_OOM};
+    }
+    p->post_slot = p->alloc<double>(len);
+  }
+  double* q = p->post_slot;
+  const double* const src[5] = {p->bmat, p->rinv, p->bvec, p->ttil, p->tvec};
+  for (int i = 0; i < 5; ++i) {
+    const int64_t cnt = i < 2 ? mm : mp;
+    GPR_HIP(hipMemcpyAsync(q, src[i], (size_t)cnt * 8, hipMemcpyDeviceToDevice, s));
+    q += cnt;
+  }
+  GPR_HIP(hipStreamSynchronize(s));
+  p->slot_observed = p->n_observed;
+  p->slot_have_b = p->have_b;
+}
+
+void do_posterior_restore(gprhip_problem* p) {
+  need_observe_state(p, "gprhip_posterior_restore");
+  if (!p->post_slot) {
+    set_error("gprhip_posterior_restore: no posterior of this model state has been saved (gprhip_posterior_save; an evaluation "
+              "and gprhip_load_predictor drop the slot)");
+    throw HipFail{ST_STATE};
+  }
+  GPR_HIP(hipSetDevice(p->device));
+  hipStream_t s = p->stream;
+  const int64_t mp = p->mp, mm = mp * mp;
+  const double* q = p->post_slot;
+  double* const dst[5] = {p->bmat, p->rinv, p->bvec, p->ttil, p->tvec};
+  for (int i = 0; i < 5; ++i) {
+    const int64_t cnt = i < 2 ? mm : mp;
+    GPR_HIP(hipMemcpyAsync(dst[i], q, (size_t)cnt * 8, hipMemcpyDeviceToDevice, s));
+    q += cnt;
+  }
+  GPR_HIP(hipStreamSynchronize(s));
+  p->n_observed = p->slot_observed;
+  p->have_b = p->slot_have_b;
+  p->pg_m_valid = false;
+  p->sp_ns_last = 0;
 }
 
 // gprhip_set_targets_many: the n x k device buffers (and the m x k ones) are made here, not inside an evaluation
@@ -4118,6 +4344,52 @@ int gprhip_load_predictor(gprhip_problem* p, const gprhip_hypers* h, const doubl
   });
 }
 
+int gprhip_observe(gprhip_problem* p, const double* inputs, int64_t ld, const double* targets, int k, double* dlog_evidence,
+                   int on_device) {
+  return guarded([&] {
+    const char* why = nullptr;
+    if (!p || !inputs) why = "invalid arguments (problem or inputs NULL)";
+    else if (k < 1 || k > GPRHIP_MAX_OBSERVE) why = "k must lie in 1 .. GPRHIP_MAX_OBSERVE (64)";
+    else if (on_device ? ld != p->D : ld < p->D) why = "bad ld (need ld == D for device buffers, ld >= D for host buffers)";
+    else if (p->f32) why = "the update runs in fp64 only (GPRHIP_F32_BULK problem)";
+    else if (p->d > 64) why = "at most 64 point dimensions on the kernel side (d)";
+    if (why) {
+      set_error(std::string("gprhip_observe: ") + why);
+      throw HipFail{ST_BAD_ARG};
+    }
+    need_observe_state(p, "gprhip_observe");
+    if ((targets == nullptr) != (p->h.model_only != 0)) {
+      set_error(p->h.model_only ? "gprhip_observe: the model state has no targets (model_only, or a predictor loaded without "
+                                  "coefficients): targets must be NULL"
+                                : "gprhip_observe: the model state has targets: targets must not be NULL");
+      throw HipFail{ST_BAD_ARG};
+    }
+    do_observe(p, inputs, ld, targets, k, dlog_evidence, on_device);
+  }, p);
+}
+
+int gprhip_posterior_save(gprhip_problem* p) {
+  return guarded([&] {
+    if (!p) {
+      set_error("gprhip_posterior_save: NULL problem");
+      throw HipFail{ST_BAD_ARG};
+    }
+    do_posterior_save(p);
+  });
+}
+
+int gprhip_posterior_restore(gprhip_problem* p) {
+  return guarded([&] {
+    if (!p) {
+      set_error("gprhip_posterior_restore: NULL problem");
+      throw HipFail{ST_BAD_ARG};
+    }
+    do_posterior_restore(p);
+  });
+}
+
+int64_t gprhip_observed_count(const gprhip_problem* p) { return p ? p->n_observed : 0; }
+
 int gprhip_condition(gprhip_problem* p, double* cond_km, double* coeff_error_bound) {
   return guarded([&] {
     if (!p) {
@@ -4262,6 +4534,34 @@ int gprhip_debug_fetch(gprhip_problem* p, const char* name, double* out, int64_t
       }
       GPR_HIP(hipSetDevice(p->device));
       fetch_upper_fortran(p, nm == "uinv" ? p->uinv : p->rinv, out);
+      return;
+    }
+    else if (nm == "rtil" || nm == "bvec") {
+      // R~ and b = R~^-T c~ as gprhip_observe reads and updates them, under the state conditions of "rinv" ("bvec": a state with
+      // targets; a loaded predictor forms b = R~ (U t) here as the first gprhip_observe would).  With "uinv" they are the whole
+      // pre-state of an update.
+      need_model(p, "gprhip_debug_fetch");
+      if (!p->have_factors || (nm == "bvec" && (p->h.model_only || p->multi_state))) {
+        set_error("gprhip_debug_fetch: \"" + nm + "\" needs the factors of an evaluation, or of a predictor loaded with "
+                  "co-variance coefficients (chol_km, r_mat)" + (nm == "bvec" ? ", and a single target vector" : ""));
+        throw HipFail{ST_STATE};
+      }
+      if (len < (nm == "rtil" ? (int64_t)p->m * p->m : (int64_t)p->m)) {
+        set_error("gprhip_debug_fetch: \"" + nm + "\" needs " + (nm == "rtil" ? "m*m" : "m") + " doubles");
+        throw HipFail{ST_BAD_ARG};
+      }
+      GPR_HIP(hipSetDevice(p->device));
+      if (nm == "rtil") {
+        fetch_upper_fortran(p, p->bmat, out);
+        return;
+      }
+      if (!p->have_b) {
+        DevBuf tmp;
+        ensure_b(p, tmp.get<double>(p->mp));
+        GPR_HIP(hipStreamSynchronize(p->stream));
+      }
+      GPR_HIP(hipMemcpyAsync(out, p->bvec, (size_t)p->m * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+      GPR_HIP(hipStreamSynchronize(p->stream));
       return;
     }
     else if (nm == "pg_m") {

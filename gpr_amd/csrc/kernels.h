@@ -422,6 +422,32 @@ void launch_path_eval(const PathEvalArgs& e, hipStream_t s);
 // e.ldg = e.d = st.D, e.rows = st.ns; st.first and st.active are not used).  No projection.
 void launch_path_refine(const PathEvalArgs& e, const RefineStepArgs& st, hipStream_t s);
 
+// ---- gprhip_observe (observe.hip): k <= 64 new observations folded into R~ and b by a triangular-pentagonal QR update
+constexpr int OBS_MAX_ROWS = 64;  // GPRHIP_MAX_OBSERVE, and the rows of the W block
+struct ObsRowsArgs {
+  const double* V;       // [>= k][mp] rows of K U^-1 at the new points
+  const double* sumsq;   // [k] |V_i|^2
+  const double* y;       // [k] targets (device), or null
+  int k, m, mp;
+  double sf2, sigma2;
+  double* W;             // out [64][mp]: V_i / sqrt(s_i); rows >= k and columns >= m exactly zero
+  double* eta;           // out [64]: y_i / sqrt(s_i) (zero without targets, and from k on)
+  double* rs;            // out [2][64]: r_i = sf2 - |V_i|^2, then s_i = r_i + sigma2
+};
+void launch_obs_rows(const ObsRowsArgs& a, hipStream_t s);
+struct ObsUpdateArgs {
+  double* R;             // row-major mp x mp upper factor R~, updated in place on and above the diagonal
+  int m, mp, k;
+  double* W;             // [64][mp] as launch_obs_rows leaves it; scratch afterwards
+  double* b;             // [mp] updated in place, or null (a state without targets: eta is not read)
+  double* eta;           // [64]; ends as rho, what the update leaves of eta
+  double* u;             // scratch [128][64]: the reflectors of the block row in flight
+  double* vb;            // scratch [2][128]: their v1, then their beta
+  double* ldr;           // scratch [mp]: log(R~'_jj / R~_jj)
+  double* out;           // out [2]: the sum of ldr in a fixed order, |rho|^2
+};
+void launch_obs_update(const ObsUpdateArgs& a, hipStream_t s);
+
 // ---- m x m finalisation (finalize.hip)
 // dst (upper tiles) = base + sum_z slices[z]; the diagonal tiles sum the first nslices_diag slices only (0 = nslices;
 // gemm_syrk_diag_slices for the result of a SYRK-shaped engine launch)

@@ -451,6 +451,29 @@ def _make_variant(spec, variational, functor, cov_kind="FITC"):
 
     Eval.Acquisition = SimpleNamespace(calc=acquisition_calc)
 
+    # ---- new observations folded into the device state without a refit (gprhip_observe, gprhip_posterior_save / _restore
+    # through Problem.observe: an extension beyond the reference's implemented surface, whose objects are immutable).
+    # MUTATING: every posterior call on that trained model (or model) reads the conditioned state afterwards; its targets,
+    # its evidence and the resident training set are not touched, and the next evaluation on the shared problem -- another
+    # model or trained object on the same inputs taking the device -- forgets the observations and drops the saved slot.
+    def _observable(owner, who):
+        if not isinstance(owner, (_Trained, _Model)):
+            raise TypeError("%s: a trained model or a model (the objects of Trained.calc / Model.calc) is needed" % who)
+        return _model_of(owner).inputs.problem
+
+    def observe(owner, inputs, targets=None, want_dlog_evidence=False):
+        """inputs: D x k points bound to the owner's inducing points, k <= 64; targets: k values for a trained model, None
+        for a model.  Returns the joint log density of the new targets given everything before them if asked for."""
+        _observable(owner, "Observe.observe")
+        return _problem_of(owner, inputs).observe(inputs.points, targets, want_dlog_evidence)
+
+    # (save / restore / count make no state: on an object whose state another evaluation has replaced, restore is the
+    #  library's state error -- the slot went with that evaluation)
+    Eval.Observe = SimpleNamespace(observe=observe,
+                                   save=lambda owner: _observable(owner, "Observe.save").posterior_save(),
+                                   restore=lambda owner: _observable(owner, "Observe.restore").posterior_restore(),
+                                   count=lambda owner: _observable(owner, "Observe.count").observed_count)
+
     # ---- posterior sample paths (gprhip_sample_paths through Problem.sample_paths: an extension beyond the reference's
     # implemented surface, whose Cov_sampler factors an nt x nt covariance).  A sampler keeps its m x n normal draws: the same
     # sampler evaluates the same n functions at any inputs.

@@ -596,6 +596,56 @@ class Problem:
                                                    _f64_ptr(r) if r is not None else None))
         del keep
 
+    # ---- observations folded into the posterior without a refit (an extension beyond the reference's surface)
+    def observe(self, inputs, targets=None, want_dlog_evidence=False, device_ptrs=None):
+        """gprhip_observe: folds k <= 64 new observations into the predictor state of the last evaluation or load_predictor --
+        a QR update of the whitened factors, O(k m^2); every posterior call then reads the conditioned model.  inputs: D x k
+        (one point per column), targets: k values, or None for a state without targets (model_only, or a predictor loaded
+        without coefficients).  The resident training set is not touched: the next eval forgets the observations.
+        device_ptrs: (inputs address, targets address or None, k) of point-major [k][D] / [k] fp64 device arrays, used
+        instead of `inputs` / `targets`.
+        Returns the joint log density of the new targets given everything before them (the evidence of the enlarged data set
+        minus the evidence before, at fixed hyper-parameters) when want_dlog_evidence, else None."""
+        dl = C.c_double(0.0)
+        dlp = C.byref(dl) if want_dlog_evidence else None
+        if device_ptrs is not None:
+            xp, yp, k = device_ptrs
+            _lib.check(self._lib.gprhip_observe(self._handle(), C.c_void_p(int(xp)), self.D,
+                                                C.c_void_p(int(yp)) if yp is not None else None, int(k), dlp, 1))
+        else:
+            x = np.asfortranarray(inputs, dtype=np.float64)
+            if x.ndim == 1:
+                if x.shape[0] != self.D:  # (a flat list of several points has no one reading)
+                    raise ValueError("observe: a 1-D input is ONE point of %d coordinates; pass several as (%d, k)" % (self.D, self.D))
+                x = np.asfortranarray(x.reshape(self.D, 1))
+            if x.ndim != 2 or x.shape[0] != self.D:
+                raise ValueError("observe: expected inputs of shape (%d, k)" % self.D)
+            k = x.shape[1]
+            y = None
+            if targets is not None:
+                y = np.ascontiguousarray(np.atleast_1d(targets), dtype=np.float64)
+                if y.shape != (k,):
+                    raise ValueError("observe: expected %d targets" % k)
+            _lib.check(self._lib.gprhip_observe(self._handle(), C.c_void_p(x.ctypes.data), self.D,
+                                                C.c_void_p(y.ctypes.data) if y is not None else None, k, dlp, 0))
+        self._sp_ns_last = 0  # (the weights of the last sample_paths call belong to the state before)
+        return dl.value if want_dlog_evidence else None
+
+    def posterior_save(self):
+        """gprhip_posterior_save: copies R~, R~^-1, b, t~, t and the observed count into the problem's one slot."""
+        _lib.check(self._lib.gprhip_posterior_save(self._handle()))
+
+    def posterior_restore(self):
+        """gprhip_posterior_restore: the saved posterior back (the slot is kept); a state error without a slot of this model
+        state -- an evaluation and load_predictor drop it."""
+        _lib.check(self._lib.gprhip_posterior_restore(self._handle()))
+        self._sp_ns_last = 0
+
+    @property
+    def observed_count(self):
+        """Observations folded in since the last evaluation or load_predictor."""
+        return int(self._lib.gprhip_observed_count(self._handle()))
+
     # ---- staged evaluation (row-sharded across devices; see gpr_amd/dist.py)
     def ar1_len(self):
         return int(self._lib.gprhip_ar1_len(self._handle()))
@@ -648,7 +698,7 @@ class Problem:
         return c.value, b.value
 
     def debug_fetch(self, name):
-        length = self.m if name == "t" else self.n
+        length = self.m if name in ("t", "bvec") else self.n
         out = np.empty(length, dtype=np.float64)
         _lib.check(self._lib.gprhip_debug_fetch(self._handle(), name.encode(), _f64_ptr(out), length))
         return out
@@ -657,7 +707,8 @@ class Problem:
         """"km": K_m of the last evaluation (m x m, upper triangle valid, zeros below); "knm_rows": the first `rows`
         rows of K_nm rebuilt with the last evaluation's kernel (rows x m); "uinv", "rinv": U^-1 and R~^-1 as the posterior
         calls read them (m x m, upper triangle, zeros below; they need the factors of an evaluation or of a predictor loaded
-        with co-variance coefficients); "pg_m": M = U^-1 (I - R~^-1 R~^-T) U^-T as the product G = K M of predict_input_grad
+        with co-variance coefficients); "rtil": R~ as stored, what `observe` updates (the same layout and conditions;
+        `debug_fetch("bvec")` gives b); "pg_m": M = U^-1 (I - R~^-1 R~^-T) U^-T as the product G = K M of predict_input_grad
         and acquire reads it (m x m, full; available once such a call has formed it -- stage "pg_m" --, until the next
         evaluation or load_predictor; `rows` = m rounded up to a multiple of 128 returns the padded matrix as it is stored);
         "sp_a": the weights A = t 1^T + U^-1 (R~^-1 Z) of the last sample_paths / sample_paths_refine call of this object, as
@@ -678,7 +729,7 @@ class Problem:
             # is asked for then, and the library, which holds the count too, refuses where that is not what it has
             ns = getattr(self, "_sp_ns_last", 0) or 1
             out = np.empty((mp, 64) if padded else (self.m, ns), dtype=np.float64, order="F")
-        elif name in ("km", "w_mat", "uinv", "rinv"):
+        elif name in ("km", "w_mat", "uinv", "rinv", "rtil"):
             out = np.empty((self.m, self.m), dtype=np.float64, order="F")
         elif name in ("knm_rows", "x_rows"):
             out = np.empty((int(rows), self.m), dtype=np.float64, order="F")

@@ -453,8 +453,8 @@ int gprhip_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const doubl
  * bad ld / ldx / ldg.  State and limits: as gprhip_acquire (GPRHIP_ESTATE under the same conditions; BOUND with kappa == 0 runs
  * the mean part alone and needs no factors).  New buffers are checked against the free device memory first (GPRHIP_EOOM).  A
  * refused call enqueues nothing; the call never changes the predictor state.
- * Limits: no optimiser other than this one (no L-BFGS, no q-batch criteria); drawn sample paths are refined by
- * gprhip_sample_paths_refine, not here; fp64 problems, one device, no multiscales.
+ * Limits: no optimiser other than this one (no L-BFGS, no q-batch criteria: greedy batches go through gprhip_observe);
+ * drawn sample paths are refined by gprhip_sample_paths_refine, not here; fp64 problems, one device, no multiscales.
  * Stage timers: "rf_small" (the persistent kernel); on the other route those of gprhip_acquire per evaluation and "rf_step". */
 enum { GPRHIP_REFINE_ST_CONVERGED = 0, GPRHIP_REFINE_ST_MAX_EVALS = 1, GPRHIP_REFINE_ST_NAN = 2 };
 #define GPRHIP_REFINE_MAX_EVALS 1000
@@ -586,6 +586,56 @@ int gprhip_co_variance_coeffs(gprhip_problem* p, double* chol_km, double* r_mat)
 int gprhip_load_predictor(gprhip_problem* p, const gprhip_hypers* h, const double* coeffs, const double* chol_km,
                           const double* r_mat);
 
+/* Folds k new observations (1 <= k <= GPRHIP_MAX_OBSERVE) into the predictor state left by the last evaluation or
+ * gprhip_load_predictor, without a refit -- what closes the loop acquire -> refine -> observe, and what greedy batch selection
+ * (kriging believer, constant liar) needs: a posterior conditioned on a fantasised observation and a cheap way back (an
+ * extension beyond the reference's implemented surface).  At fixed hyper-parameters and inducing points a training point
+ * enters the FITC posterior only through its row v = K_xm U^-1, s = sf2 - |v|^2 + sigma2 and y (lib/fitc_gp.ml:151-182; the
+ * variational model has the same posterior, only l1 differs, :262-263).  With w_i = v_i / sqrt(s_i), eta_i = y_i / sqrt(s_i):
+ *   B~' = B~ + sum w_i w_i^T,  c~' = c~ + sum w_i eta_i,  so [R~' | b'] is the triangular factor of [R~ | b] stacked on [W | eta]
+ * -- a triangular-pentagonal QR update, O(k m^2), orthogonal, in the whitened coordinates; then
+ * R~'^-1, t~' = R~'^-1 b' and t' = U^-1 t~'.
+ *   inputs: on_device = 0: HOST, Fortran D x k (ld >= D); on_device = 1: device, point-major [k][D] (ld == D).
+ *   targets: k doubles in the same memory space.  A state without targets (model_only = 1, or a predictor loaded without
+ *            coefficients) takes targets == NULL and updates the factors only; a state with targets refuses NULL.
+ *   dlog_evidence (HOST, may be NULL): the joint log density of the new targets given everything before them, i.e. the
+ *            evidence of the enlarged data set minus the evidence before, at fixed hyper-parameters:
+ *              dl1 = -1/2 (2 sum_j log(R~'_jj / R~_jj) + sum_i log s_i + k log 2 pi)   (-1/2 sum_i r_i / s_i more when the
+ *                    state's evaluation was variational; r_i = sf2 - |v_i|^2)
+ *              dl2 = -1/2 |rho|^2,  rho = what the QR leaves of eta  (|eta|^2 + |b|^2 = |b'|^2 + |rho|^2)
+ *            Without targets it holds dl1 alone.
+ * Afterwards every posterior call reads the conditioned model: gprhip_predict, gprhip_predict_input_grad, gprhip_acquire,
+ * gprhip_acquire_refine, gprhip_sample_paths, gprhip_sample_paths_refine, gprhip_covariances, gprhip_train_stats,
+ * gprhip_co_variance_coeffs -- a model file saved afterwards holds the conditioned predictor.  The matrix M of
+ * gprhip_predict_input_grad and the weights of gprhip_sample_paths are formed again at their next use (debug names "pg_m" and
+ * "sp_a" are GPRHIP_ESTATE until then; "w_mat" is scratch of the update).  The condition estimate stays: K_m is unchanged.
+ * WHAT DOES NOT CHANGE: the resident training set (inputs, targets, V and the validity of reuse_v).  The next gprhip_eval
+ * recomputes from the n original rows and FORGETS the observations; gprhip_train_stats goes over the n resident rows only.
+ * GPRHIP_EBADARG: k out of range, bad ld, a non-finite input or target (device buffers are read back once to be checked), a
+ *   GPRHIP_F32_BULK problem, multiscales in the model state, more than 64 point dimensions on the kernel side, targets given
+ *   to a state without targets or withheld from one with them.
+ * GPRHIP_ESTATE: no model, a predictor loaded without factors, after gprhip_eval_targets, an evaluation in flight.
+ * GPRHIP_ENOTPOSDEF: some s_i <= 0 (possible at sigma2 = 0 on an inducing point).  The k values of s come back to the host
+ *   BEFORE anything of the state is written: a refused call leaves every bit of the state as it was.
+ * GPRHIP_EOOM: the scratch of the first call ((64 + 2) mp + 8.7 K doubles) against the free device memory.
+ * No atomics: two runs give the same bits.  Stage timers: "obs_rows" (K, V = K U^-1 by gprhip_predict's launches, then W and
+ * eta), "obs_update" (the QR update: per 128-column block row one diagonal launch and one trailing launch), "obs_inverse"
+ * (R~'^-1 by the inverse pass of gprhip_load_predictor, O(m^3)), "obs_vectors" (t~', t').
+ *
+ * gprhip_posterior_save copies R~, R~^-1, b, t~, t (2 mp^2 + 3 mp doubles, mp = m rounded up to 128, device to device) and the
+ * observed count into ONE slot, allocated at the first save after a comparison with the free device memory (GPRHIP_EOOM);
+ * gprhip_posterior_restore copies them back and keeps the slot, so it may be used again.  An evaluation,
+ * gprhip_load_predictor and gprhip_problem_destroy drop the slot: gprhip_posterior_restore without a saved slot of this model
+ * state is GPRHIP_ESTATE.  Both need the state gprhip_observe needs.  The batch loop:
+ *   save -> observe(fantasy) -> acquire -> observe(fantasy) -> ... -> restore.
+ * gprhip_observed_count: observations folded in since the last evaluation or gprhip_load_predictor. */
+#define GPRHIP_MAX_OBSERVE 64
+int gprhip_observe(gprhip_problem* p, const double* inputs, int64_t ld, const double* targets, int k,
+                   double* dlog_evidence, int on_device);
+int gprhip_posterior_save(gprhip_problem* p);      /* one slot: R~, R~^-1, b, t~, t and the observed count */
+int gprhip_posterior_restore(gprhip_problem* p);   /* GPRHIP_ESTATE without a saved slot of this model state */
+int64_t gprhip_observed_count(const gprhip_problem* p);
+
 /* Conditioning of the inducing covariance of the current model state: *cond_km = an estimate (power iteration on
  * U^T U and U^-1 U^-T, a lower bound within a small factor) of the 2-norm condition number of K_m + jitter, and
  * *coeff_error_bound = cond_km * unit roundoff of the n x m operands (2^-24 for GPRHIP_F32_BULK, 2^-53 for GPRHIP_F64):
@@ -610,6 +660,10 @@ int gprhip_condition(gprhip_problem* p, double* cond_km, double* coeff_error_bou
  *   "uinv", "rinv" m*m : U^-1 and R~^-1 as gprhip_predict, gprhip_covariances and the other posterior calls read them,
  *               Fortran m x m, upper triangle, zeros below -- after gprhip_eval, gprhip_eval_targets, or a
  *               gprhip_load_predictor with co-variance coefficients (GPRHIP_ESTATE otherwise).  A copy: the state is untouched.
+ *   "rtil" m*m : R~ as stored (R = R~ U is the reference's r_mat), Fortran m x m, upper triangle, zeros below; "bvec" m : b =
+ *               R~^-T c~ (= Q_n^T y~, lib/fitc_gp.ml:285-286) -- what gprhip_observe reads and updates, under the state
+ *               conditions of "rinv" ("bvec": a state with one target vector; a loaded predictor forms b = R~ (U t) first, as
+ *               its first gprhip_observe would).
  *   "pg_m" m*m : M = U^-1 (I - R~^-1 R~^-T) U^-T as the product G = K M of gprhip_predict_input_grad and gprhip_acquire reads
  *               it, Fortran m x m, full -- once a call of either has asked for a variance part with more than 64 inducing
  *               points or more than 16 point dimensions (stage "pg_m"), until the next evaluation or gprhip_load_predictor

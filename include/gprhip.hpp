@@ -759,6 +759,36 @@ struct Make_deriv {
         return r;
       }
     };
+    // New observations folded into the device state of a trained model or a model without a refit (gprhip_observe,
+    // gprhip_posterior_save / _restore: an extension beyond the reference's implemented surface, whose objects are immutable).
+    // MUTATING: every posterior call on that object reads the conditioned state afterwards; the object's targets, its
+    // evidence and the resident training set are not touched, and the next evaluation on the shared problem forgets the
+    // observations and drops the saved slot.  in.points: D x k, k <= GPRHIP_MAX_OBSERVE; a model takes no targets.
+    struct Observe {
+      static double observe(const Trained_t& trained, const Inputs_t& in, const Vec& targets) {
+        Problem& p = problem_for(trained, in, "Observe.observe");
+        if ((int64_t)targets.size() != in.points->cols)
+          throw std::invalid_argument("Observe.observe: one target per new point");
+        double dl = 0.0;
+        check(gprhip_observe(p.get(), in.points->data(), in.points->rows, targets.data(), (int)in.points->cols, &dl, 0));
+        return dl;  // the joint log density of the new targets given everything before them
+      }
+      static double observe(const Model_t& model, const Inputs_t& in) {
+        Problem& p = problem_for(model, in, "Observe.observe");
+        double dl = 0.0;
+        check(gprhip_observe(p.get(), in.points->data(), in.points->rows, nullptr, (int)in.points->cols, &dl, 0));
+        return dl;  // dl1 alone
+      }
+      // (no state is made here: a save or restore on an object whose state another evaluation has replaced is GPRHIP_ESTATE
+      //  or acts on that other state -- the caller keeps save / observe / restore together)
+      template <typename Owner> static void save(const Owner& o) { check(gprhip_posterior_save(o_problem(o).get())); }
+      template <typename Owner> static void restore(const Owner& o) { check(gprhip_posterior_restore(o_problem(o).get())); }
+      template <typename Owner> static int64_t count(const Owner& o) { return gprhip_observed_count(o_problem(o).get()); }
+
+     private:
+      static Problem& o_problem(const Trained_t& t) { return *t.model.inputs.problem; }
+      static Problem& o_problem(const Model_t& m) { return *m.inputs.problem; }
+    };
     // Posterior sample paths (gprhip_sample_paths: an extension beyond the reference's implemented surface).  A sampler keeps
     // the caller's m x ns standard normal draws z: the same sampler evaluates the same ns functions at any inputs.
     struct Path_sampler_t {
