@@ -113,12 +113,10 @@ def hypers_of(c, args):
                 log_ms=args.get("log_multiscales_m05"), bulk32=c.f32)
 
 
-@functools.lru_cache(maxsize=None)
-def points(c, nt):
-    """(test inputs D x nt, mask of the far points): entry i is of kind i mod 5 -- a training input, an inducing point,
-    a training input moved half a spread, a point beyond the reach of every inducing point, an inducing point moved half a
-    spread.  The period 5 walks every kind through every position of the 4-, 16-, 64- and 256-row blocks of the kernels."""
-    X, y, Z, args = data(c)
+def points_of(X, Z, args, nt):
+    """The fixed mix of points() for any training inputs X (D x n), inducing points Z (d x m) and keyword arguments of
+    Problem.eval: (test inputs D x nt, mask of the far points)."""
+    n, (d, m) = X.shape[1], Z.shape
     tp = args.get("tproj")
     lift = (lambda p: p) if tp is None else (lambda p: tp @ np.linalg.solve(tp.T @ tp, p))
     rng = np.random.default_rng(77 + nt)
@@ -129,21 +127,31 @@ def points(c, nt):
     for i in range(nt):
         kind = i % 5
         if kind == 0:
-            Xt[:, i] = X[:, (7 * i) % c.n]
+            Xt[:, i] = X[:, (7 * i) % n]
         elif kind == 1:
-            Xt[:, i] = lift(Z[:, (3 * i) % c.m])
+            Xt[:, i] = lift(Z[:, (3 * i) % m])
         elif kind == 2:
-            Xt[:, i] = X[:, (5 * i) % c.n] + 0.5 * X.std() * rng.normal(size=X.shape[0]) / np.sqrt(X.shape[0])
+            Xt[:, i] = X[:, (5 * i) % n] + 0.5 * X.std() * rng.normal(size=X.shape[0]) / np.sqrt(X.shape[0])
         elif kind == 4:
-            Xt[:, i] = lift(Z[:, (11 * i) % c.m] + 0.5 * Z.std() * rng.normal(size=c.d) / np.sqrt(c.d))
+            Xt[:, i] = lift(Z[:, (11 * i) % m] + 0.5 * Z.std() * rng.normal(size=d) / np.sqrt(d))
         else:
-            e = np.zeros(c.d)
-            e[i % c.d] = reach * (1.0 + 0.1 * rng.uniform())
-            Xt[:, i] = lift(Z[:, i % c.m] + e)
+            e = np.zeros(d)
+            e[i % d] = reach * (1.0 + 0.1 * rng.uniform())
+            Xt[:, i] = lift(Z[:, i % m] + e)
             far[i] = True
     Xt = np.asfortranarray(Xt)
     Xt.setflags(write=False)
     return Xt, far
+
+
+@functools.lru_cache(maxsize=None)
+def points(c, nt):
+    """(test inputs D x nt, mask of the far points): entry i is of kind i mod 5 -- a training input, an inducing point,
+    a training input moved half a spread, a point beyond the reach of every inducing point, an inducing point moved half a
+    spread.  The period 5 walks every kind through every position of the 4-, 16-, 64- and 256-row blocks of the kernels."""
+    X, y, Z, args = data(c)
+    assert X.shape[1] == c.n and Z.shape == (c.d, c.m)
+    return points_of(X, Z, args, nt)
 
 
 def _frozen(g):
@@ -217,19 +225,18 @@ def predict_raw(p, Xt, predictive, want_means, want_vars):
     return mu, var
 
 
-def check_predict(p, c, nt, ops, label, means=True):
-    """means, variances (predictive and not; together and each alone) at the fixed mix of nt test points"""
-    Xt, far = points(c, nt)
-    g = geometry(c, nt)
-    label = "%s-nt%d" % (label, nt)
-    sf2 = math.exp(c.log_sf2)        # the host's libm, as the library's exp(log_sf2)
+def check_predict_at(p, Xt, far, g, sigma2, log_sf2, ops, label, means=True, predict=None):
+    """check_predict at given test points Xt with their 80-bit geometry g, on whatever state `ops` was fetched from;
+    predict(Xt, predictive, want_means, want_vars) stands in for the device where given"""
+    predict = predict or (lambda *a: predict_raw(p, *a))
+    sf2 = math.exp(log_sf2)        # the host's libm, as the library's exp(log_sf2)
     ch = R.chain(g, ops.uinv, ops.rinv)
     mu_ref, mu_b = R.mean(g, ops.t) if means else (None, None)
     for predictive in (False, True):
-        add = c.sigma2 if predictive else 0.0
+        add = sigma2 if predictive else 0.0
         var_ref, var_b = R.variance(g, ch, add)
         for want_m, want_v in ((means, True), (False, True)) + (((True, False),) if means else ()):
-            mu, var = predict_raw(p, Xt, predictive, want_m, want_v)
+            mu, var = predict(Xt, predictive, want_m, want_v)
             if want_m:
                 hold(label, "mean", mu, mu_ref, mu_b)
                 assert np.all(mu[far] == 0.0) and not np.any(np.signbit(mu[far])), label
@@ -237,6 +244,12 @@ def check_predict(p, c, nt, ops, label, means=True):
                 hold(label, "variance", var, var_ref, var_b)
                 assert np.all(var[far] == (sf2 - 0.0) + add), label
     return var_ref, var_b
+
+
+def check_predict(p, c, nt, ops, label, means=True):
+    """means, variances (predictive and not; together and each alone) at the fixed mix of nt test points"""
+    Xt, far = points(c, nt)
+    return check_predict_at(p, Xt, far, geometry(c, nt), c.sigma2, c.log_sf2, ops, "%s-nt%d" % (label, nt), means)
 
 
 # ---- predict ------------------------------------------------------------------------------------------------------------------
@@ -373,15 +386,13 @@ def test_every_mean_of_every_target_column(c, k, monkeypatch):
 
 
 # ---- covariances, cov_samples -------------------------------------------------------------------------------------------------
-def check_covariances(p, c, nt, ops, label):
-    Xt, far = points(c, nt)
-    g = geometry(c, nt)
+def check_covariances_at(p, Xt, g, sigma2, ops, label):
+    """check_covariances at given test points Xt with their 80-bit geometry g, on whatever state `ops` was fetched from"""
     ch = R.chain(g, ops.uinv, ops.rinv)
-    label = "%s-nt%d" % (label, nt)
     out = {}
     for kind in ("FITC", "FIC"):
         for predictive in (False, True):
-            add = c.sigma2 if predictive else 0.0
+            add = sigma2 if predictive else 0.0
             cov = p.covariances(Xt, kind=kind, predictive=predictive)
             ref, bound = R.covariances(g, ch, kind, add)
             hold(label, kind + (".predictive" if predictive else ""), cov, ref, bound)
@@ -394,6 +405,10 @@ def check_covariances(p, c, nt, ops, label):
     M.record("post.fitc_diag_vs_variance", float(np.max(gap / (np.diag(cb) + var_b))), 1.0, case=label)
     assert np.all(gap <= np.diag(cb) + var_b), label
     return out["FITC", False]
+
+
+def check_covariances(p, c, nt, ops, label):
+    return check_covariances_at(p, points(c, nt)[0], geometry(c, nt), c.sigma2, ops, "%s-nt%d" % (label, nt))
 
 
 @gpu
