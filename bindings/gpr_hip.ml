@@ -54,6 +54,10 @@ external predict_input_grad : problem -> mat -> mat option -> mat option -> unit
 (* an acquisition criterion over the points and its gradient with respect to them (gprhip_acquire); the vector is
    [| kind; maximise; predictive; best; xi; kappa; var_floor |], kind 0 EI, 1 log EI, 2 PI, 3 bound *)
 external acquire : problem -> vec -> mat -> vec option -> mat option -> unit = "gprhip_ml_acquire"
+(* max-value entropy search over the points and its gradient (gprhip_acquire_max_value): extremes (of 1 .. 64 drawn paths:
+   maxima when maximising, else minima) -> maximise -> var_floor -> points -> values -> dvalues *)
+external acquire_max_value : problem -> vec -> bool -> float -> mat -> vec option -> mat option -> unit
+  = "gprhip_ml_acquire_max_value_bc" "gprhip_ml_acquire_max_value"
 (* refines the starts (D x ns) of an acquisition criterion inside a box by projected gradient ascent
    (gprhip_acquire_refine): params as acquire -> options [| max_evals; step0; c1; shrink; grow; xtol |] -> box (D x 2: lower,
    upper) -> starts -> x_out (D x ns) -> values (ns) *)

@@ -192,6 +192,34 @@ CAMLprim value gprhip_ml_acquire(value prob, value params, value points, value v
   CAMLreturn(Val_unit);
 }
 
+/* external acquire_max_value : problem -> vec -> bool -> float -> mat -> values:vec option -> dvalues:mat option -> unit
+ *   max-value entropy search over the points and its gradient (D x nt) from the extremes of drawn paths
+ *   (gprhip_acquire_max_value): extremes -> maximise -> var_floor -> points */
+CAMLprim value gprhip_ml_acquire_max_value(value prob, value extremes, value maximise, value var_floor, value points,
+                                           value values, value dvalues) {
+  CAMLparam5(prob, extremes, maximise, var_floor, points);
+  CAMLxparam2(values, dvalues);
+  struct caml_ba_array* ba = Caml_ba_array_val(points);
+  gprhip_problem* p = Problem_val(prob);
+  const double* x = (const double*)ba->data;
+  int64_t ld = ba->dim[0], nt = ba->dim[1];
+  double* a = (double*)opt_data(values);
+  double* da = (double*)opt_data(dvalues);
+  const double* e = (const double*)Caml_ba_data_val(extremes);
+  int n = (int)Caml_ba_array_val(extremes)->dim[0], s = Bool_val(maximise);
+  double floor = Double_val(var_floor);
+  int status;
+  caml_release_runtime_system();
+  status = gprhip_acquire_max_value(p, e, n, s, floor, x, ld, nt, a, da, ld, NULL, NULL, 0, NULL, NULL, NULL, 0);
+  caml_acquire_runtime_system();
+  check(status);
+  CAMLreturn(Val_unit);
+}
+CAMLprim value gprhip_ml_acquire_max_value_bc(value* argv, int argn) {
+  (void)argn;
+  return gprhip_ml_acquire_max_value(argv[0], argv[1], argv[2], argv[3], argv[4], argv[5], argv[6]);
+}
+
 /* external acquire_refine : problem -> vec -> vec -> mat -> mat -> mat -> vec -> unit
  *   refines the starts (D x ns) of an acquisition criterion inside a box (gprhip_acquire_refine): params as acquire,
  *   options [| max_evals; step0; c1; shrink; grow; xtol |], box D x 2 (lower, upper), x_out D x ns, values ns */

@@ -114,6 +114,7 @@ REFINE_MAX_EVALS = 1000   # GPRHIP_REFINE_MAX_EVALS
 REFINE_MAX_STARTS = 4096  # GPRHIP_REFINE_MAX_STARTS
 MAX_TOP_K = 64    # GPRHIP_MAX_TOP_K
 MAX_DRAWS = 64    # GPRHIP_MAX_DRAWS
+MAX_EXTREMES = 64  # GPRHIP_MAX_EXTREMES
 MAX_TARGETS = 16  # GPRHIP_MAX_TARGETS
 MAX_BATCH = 64    # GPRHIP_MAX_BATCH
 MAX_OBSERVE = 64  # GPRHIP_MAX_OBSERVE
@@ -152,6 +153,8 @@ SIGNATURES = {
     "gprhip_predict_input_grad": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, _vp, _vp, _vp, _vp, C.c_int64, C.c_int]),
     "gprhip_acquire": (C.c_int, [_vp, C.POINTER(Acquisition), _vp, C.c_int64, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, C.c_int,
                                  C.POINTER(C.c_int64), _dp, _dp, C.c_int]),
+    "gprhip_acquire_max_value": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_double, _vp, C.c_int64, C.c_int64, _vp, _vp, C.c_int64,
+                                           _vp, _vp, C.c_int, C.POINTER(C.c_int64), _dp, _dp, C.c_int]),
     "gprhip_acquire_refine": (C.c_int, [_vp, C.POINTER(Acquisition), C.POINTER(RefineOptions), _dp, _dp, _dp, _vp, C.c_int64, C.c_int64,
                                         _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int]),
     "gprhip_sample_paths": (C.c_int, [_vp, _dp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int, _vp, C.c_int64,

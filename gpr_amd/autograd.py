@@ -12,7 +12,8 @@ inputs (gprhip_predict_input_grad, on_device = 1) -- an acquisition function ove
 through the model, a feature extractor in front of the GP at prediction time.
 
 `acquire(problem, test_inputs, kind, ...)` is an acquisition criterion over candidate points (expected improvement, its
-logarithm, probability of improvement, a confidence bound) as a differentiable function of them (gprhip_acquire, on_device = 1).
+logarithm, probability of improvement, a confidence bound) as a differentiable function of them (gprhip_acquire, on_device = 1);
+`acquire_max_value(problem, test_inputs, extremes, ...)` is max-value entropy search in the same way (gprhip_acquire_max_value).
 
 torch is imported when `log_evidence`, `predict` or `acquire` is first called, not with this module: `import gpr_amd` never starts importing it.
 """
@@ -179,6 +180,7 @@ def predict(problem, test_inputs, predictive=True):
 
 
 _acquire_fn = None
+_MAX_VALUE = object()  # the `kind` of acquire_max_value inside _Acquire: Problem.acquire_max_value instead of Problem.acquire
 
 
 def _acquire_function():
@@ -207,7 +209,10 @@ def _acquire_function():
             # the library works on its own stream: what produced the tensor must be complete before it reads it (its own
             # outputs are complete when the call returns)
             torch.cuda.current_stream(x.device).synchronize()
-            problem.acquire(x.data_ptr(), kind, want=tuple(ptrs), out_device_ptrs=ptrs, nt=nt, **kw)
+            if kind is _MAX_VALUE:
+                problem.acquire_max_value(x.data_ptr(), want=tuple(ptrs), out_device_ptrs=ptrs, nt=nt, **kw)
+            else:
+                problem.acquire(x.data_ptr(), kind, want=tuple(ptrs), out_device_ptrs=ptrs, nt=nt, **kw)
             return values
 
         @staticmethod
@@ -230,3 +235,14 @@ def acquire(problem, test_inputs, kind, **kw):
     if extra:
         raise TypeError("acquire: unknown arguments %s" % sorted(extra))
     return _acquire_function().apply(problem, kind, dict(kw), test_inputs)
+
+
+def acquire_max_value(problem, test_inputs, extremes, **kw):
+    """Max-value entropy search (Problem.acquire_max_value) of `problem`'s current model state at `test_inputs`, an (nt, D)
+    contiguous float64 tensor on the problem's device, as an (nt,) float64 tensor ("larger is better").  extremes: the extreme
+    values of 1 .. 64 drawn paths (host numbers: they are constants of the graph); kw: maximise (required), var_floor.  One
+    library call runs in forward; backward returns g[:, None] * dvalues."""
+    extra = set(kw) - {"maximise", "var_floor"}
+    if extra:
+        raise TypeError("acquire_max_value: unknown arguments %s" % sorted(extra))
+    return _acquire_function().apply(problem, _MAX_VALUE, dict(kw, extremes=extremes), test_inputs)

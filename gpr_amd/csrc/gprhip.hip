@@ -280,6 +280,8 @@ struct gprhip_problem {
   double* pg_buf = nullptr;  // gradient staging of one chunk: [2][rows][D] for a host destination + [2][rows][d] dp (projection)
   int64_t pg_rows = 0;       // rows it holds
   bool pg_host = false, pg_proj = false;  // ... with those two parts
+  // gprhip_acquire_max_value: the extremes of the call on the device and their pinned mirror [GPRHIP_MAX_EXTREMES each]
+  double *mv_extremes = nullptr, *mv_host = nullptr;
   // gprhip_acquire's selection: candidate lists of the slabs (device), the block of a piece's k winners [k (D + 2)] on the
   // device and its pinned mirror; made at the first call with top_k > 0
   void* acq_scratch = nullptr;
@@ -2170,9 +2172,9 @@ PgPlan pg_prepare(gprhip_problem* p, const char* fn, int64_t nt, bool want_var, 
 // One chunk of the prediction gradient on the device: K and G = K M where the plan keeps them in memory, then the gradient
 // kernel (predict_grad.hip; the one-kernel variant for few inducing points) and the back-projection of its d/dp where the
 // model has a projection.  dst[q]: where the [rows][D] gradients end up (mean, variance; null: not wanted); acq: the criterion
-// epilogue of gprhip_acquire, whose one gradient goes to dst[0].
+// epilogue of gprhip_acquire, mv: that of gprhip_acquire_max_value (at most one of the two), whose one gradient goes to dst[0].
 void pg_chunk(gprhip_problem* p, const PgPlan& plan, const double* pts, int rows, int rows_p, bool want_var, double add,
-              double* mean_dev, double* var_dev, double* const dst[2], const AcqArgs* acq) {
+              double* mean_dev, double* var_dev, double* const dst[2], const AcqArgs* acq, const MvArgs* mv = nullptr) {
   hipStream_t s = p->stream;
   const int mp = p->mp, D = p->D, d = p->d;
   const bool proj = p->has_proj();
@@ -2185,7 +2187,8 @@ void pg_chunk(gprhip_problem* p, const PgPlan& plan, const double* pts, int rows
     a.cp = p->cp; a.pts = pts; a.Z = p->Z; a.shift = p->zshift; a.uinv = p->uinv; a.rinv = p->rinv; a.tvec = p->tvec;
     a.rows = rows; a.m = p->m; a.mp = mp; a.d = d; a.want_var = want_var ? 1 : 0; a.add = add;
     a.means = mean_dev; a.vars = var_dev; a.dmeans = kout[0]; a.dvars = kout[1]; a.ldg = kld;
-    if (acq) launch_small_acquire_grad(a, *acq, s);
+    if (mv) launch_small_max_value_grad(a, *mv, s);
+    else if (acq) launch_small_acquire_grad(a, *acq, s);
     else launch_small_predict_grad(a, s);
   } else {
     if (plan.mats) {
@@ -2205,7 +2208,8 @@ void pg_chunk(gprhip_problem* p, const PgPlan& plan, const double* pts, int rows
     a.rows = rows; a.m = p->m; a.mp = mp; a.d = d;
     a.log_sf2 = p->cp.log_sf2; a.inv_ell2_05 = p->cp.inv_ell2_05; a.sf2 = p->cp.sf2; a.add = add;
     a.means = mean_dev; a.vars = var_dev; a.dmeans = kout[0]; a.dvars = kout[1]; a.ldg = kld;
-    if (acq) launch_acquire_grad(a, *acq, s);
+    if (mv) launch_max_value_grad(a, *mv, s);
+    else if (acq) launch_acquire_grad(a, *acq, s);
     else launch_predict_grad(a, s);
   }
   if (proj)
@@ -2273,19 +2277,29 @@ AcqArgs acq_args(const gprhip_acquisition* acq) {
 // gprhip_acquire: the chunk loop of do_predict_input_grad with the criterion epilogue of the two kernels -- one value vector and
 // one gradient matrix instead of two --, and the best top_k candidates selected on the device chunk by chunk (acquire.hip),
 // the chunks' lists merged here with the same rule: value descending, the lower index first among equal values.
-// The caller has checked the arguments and the limits.
-void do_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const double* test_inputs, int64_t ld, int64_t nt,
-                double* values, double* dvalues, int64_t ldg, double* means, double* variances, int top_k, int64_t* top_index,
-                double* top_values, double* top_dvalues, int on_device) {
-  const bool want_var = acq_wants_var(acq) || variances;
-  need_posterior_state(p, "gprhip_acquire", "predict from", true, want_var, true,
+// The caller has checked the arguments and the limits.  The criterion is q (gprhip_acquire) or, where mv is not null, max-value
+// entropy search over host_extremes (gprhip_acquire_max_value), which are uploaded once the call can no longer be refused.
+void acquire_walk(gprhip_problem* p, const char* fn, bool want_var, double add, AcqArgs q, MvArgs* mv, const double* host_extremes,
+                  const double* test_inputs, int64_t ld, int64_t nt, double* values, double* dvalues, int64_t ldg, double* means,
+                  double* variances, int top_k, int64_t* top_index, double* top_values, double* top_dvalues, int on_device) {
+  need_posterior_state(p, fn, "predict from", true, want_var, true,
                        "means and their gradients are available after the next gprhip_eval");
   GPR_HIP(hipSetDevice(p->device));
   hipStream_t s = p->stream;
   const int D = p->D;
   const bool want_grad = dvalues || (top_k > 0 && top_dvalues);
   const bool stage_grad = want_grad && !(on_device && dvalues);  // the gradient of a chunk stays in the library's staging
-  const PgPlan plan = pg_prepare(p, "gprhip_acquire", nt, want_var, stage_grad);
+  const PgPlan plan = pg_prepare(p, fn, nt, want_var, stage_grad);
+  if (mv) {
+    if (!p->mv_extremes) {
+      p->mv_extremes = p->alloc<double>(GPRHIP_MAX_EXTREMES);
+      GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->mv_host), GPRHIP_MAX_EXTREMES * sizeof(double), hipHostMallocDefault));
+    }
+    // (every earlier call has synchronised the stream before it returned: the mirror is free)
+    std::copy(host_extremes, host_extremes + mv->n, p->mv_host);
+    GPR_HIP(hipMemcpyAsync(p->mv_extremes, p->mv_host, (size_t)mv->n * sizeof(double), hipMemcpyHostToDevice, s));
+    mv->extremes = p->mv_extremes;
+  }
   if (top_k > 0 && !p->acq_scratch) {
     p->acq_scratch = p->alloc<char>(acq_select_scratch_bytes());
     p->acq_out = p->alloc<double>((int64_t)ACQ_MAX_TOP_K * (D + 2));
@@ -2293,8 +2307,6 @@ void do_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const double* 
                           hipHostMallocDefault));
   }
   if (plan.mats) ensure_predict_m(p);
-  AcqArgs q = acq_args(acq);
-  const double add = acq->predictive ? p->h.sigma2 : 0.0;
   SpBest best;  // the best so far, over the chunks done
   walk_chunks(p, plan.chunk, test_inputs, ld, nt, on_device, [&](int64_t lo, int rows, int rows_p, const double*, const double* pts) {
     double* const mean_dev = means ? (on_device ? means + lo : plan.rmean) : nullptr;
@@ -2303,7 +2315,8 @@ void do_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const double* 
     double* const dst = want_grad ? (stage_grad ? plan.stage_g[0] : dvalues + lo * D) : nullptr;
     double* const dsts[2] = {dst, nullptr};
     q.values = val_dev;
-    pg_chunk(p, plan, pts, rows, rows_p, want_var, add, mean_dev, var_dev, dsts, &q);
+    if (mv) mv->values = val_dev;
+    pg_chunk(p, plan, pts, rows, rows_p, want_var, add, mean_dev, var_dev, dsts, mv ? nullptr : &q, mv);
     if (!on_device) {
       if (values) GPR_HIP(hipMemcpyAsync(values + lo, val_dev, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, s));
       if (means) GPR_HIP(hipMemcpyAsync(means + lo, plan.rmean, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -2334,6 +2347,25 @@ void do_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const double* 
   });
   write_topk(best, top_k, D, top_index, top_values, top_dvalues);
   if (p->timer.on) tcollect(p);
+}
+
+void do_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const double* test_inputs, int64_t ld, int64_t nt,
+                double* values, double* dvalues, int64_t ldg, double* means, double* variances, int top_k, int64_t* top_index,
+                double* top_values, double* top_dvalues, int on_device) {
+  acquire_walk(p, "gprhip_acquire", acq_wants_var(acq) || variances, acq->predictive ? p->h.sigma2 : 0.0, acq_args(acq), nullptr,
+               nullptr, test_inputs, ld, nt, values, dvalues, ldg, means, variances, top_k, top_index, top_values, top_dvalues,
+               on_device);
+}
+
+// gprhip_acquire_max_value: the walk of gprhip_acquire with the epilogue of mv_math.h; the latent variance, always needed
+void do_acquire_max_value(gprhip_problem* p, const double* extremes, int n_extremes, int maximise, double var_floor,
+                          const double* test_inputs, int64_t ld, int64_t nt, double* values, double* dvalues, int64_t ldg,
+                          double* means, double* variances, int top_k, int64_t* top_index, double* top_values,
+                          double* top_dvalues, int on_device) {
+  MvArgs mv;
+  mv.n = n_extremes; mv.s = maximise ? 1.0 : -1.0; mv.var_floor = var_floor; mv.extremes = nullptr; mv.values = nullptr;
+  acquire_walk(p, "gprhip_acquire_max_value", true, 0.0, AcqArgs{}, &mv, extremes, test_inputs, ld, nt, values, dvalues, ldg,
+               means, variances, top_k, top_index, top_values, top_dvalues, on_device);
 }
 
 // ---- what gprhip_acquire_refine and gprhip_sample_paths_refine share: one arena (rf_buf), one library-side loop
@@ -3665,6 +3697,7 @@ void gprhip_problem_destroy(gprhip_problem* p) {
   if (p->hy_host && !p->is_lane) hipHostFree(p->hy_host);
   if (p->res_host) hipHostFree(p->res_host);
   if (p->acq_host) hipHostFree(p->acq_host);
+  if (p->mv_host) hipHostFree(p->mv_host);
   if (p->rf_active) hipHostFree(p->rf_active);
   if (p->sp_zhost) hipHostFree(p->sp_zhost);
   if (p->sp_host) hipHostFree(p->sp_host);
@@ -4162,6 +4195,35 @@ int gprhip_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const doubl
     }
     do_acquire(p, acq, test_inputs, ld, nt, values, dvalues, ldg, means, variances, top_k, top_index, top_values, top_dvalues,
                on_device);
+  }, p);
+}
+
+int gprhip_acquire_max_value(gprhip_problem* p, const double* extremes, int n_extremes, int maximise, double var_floor,
+                             const double* test_inputs, int64_t ld, int64_t nt, double* values, double* dvalues, int64_t ldg,
+                             double* means, double* variances, int top_k, int64_t* top_index, double* top_values,
+                             double* top_dvalues, int on_device) {
+  return guarded([&] {
+    auto refuse = [](const char* why) {
+      set_error(std::string("gprhip_acquire_max_value: ") + why);
+      throw HipFail{ST_BAD_ARG};
+    };
+    if (n_extremes < 1 || n_extremes > GPRHIP_MAX_EXTREMES) refuse("n_extremes must lie in 1 .. GPRHIP_MAX_EXTREMES (64)");
+    if (!extremes) refuse("invalid arguments (extremes is NULL)");
+    for (int j = 0; j < n_extremes; ++j)
+      if (!std::isfinite(extremes[j])) refuse("the extremes must be finite");
+    if (!(var_floor > 0.0) || !std::isfinite(var_floor)) refuse("var_floor must be positive and finite");
+    if (top_k < 0 || top_k > GPRHIP_MAX_TOP_K) refuse("top_k must lie in 0 .. GPRHIP_MAX_TOP_K (64)");
+    if (top_k > 0 && !top_index) refuse("top_k > 0 needs top_index");
+    if (!values && !dvalues && !means && !variances && top_k == 0)
+      refuse("nothing is requested (the four outputs are NULL and top_k is 0)");
+    if (!p || !test_inputs || nt < 1) refuse("invalid arguments");
+    if (p->f32) refuse("the prediction gradient is evaluated in fp64 only (GPRHIP_F32_BULK problem)");
+    if (p->d > 64) refuse("at most 64 point dimensions on the kernel side (d)");
+    if (on_device ? ld != p->D : ld < p->D) refuse("bad ld (need ld == D for device buffers, ld >= D for host buffers)");
+    if (dvalues && (on_device ? ldg != p->D : ldg < p->D))
+      refuse("bad ldg (need ldg == D for device buffers, ldg >= D for host buffers)");
+    do_acquire_max_value(p, extremes, n_extremes, maximise, var_floor, test_inputs, ld, nt, values, dvalues, ldg, means, variances,
+                         top_k, top_index, top_values, top_dvalues, on_device);
   }, p);
 }
 

@@ -315,6 +315,19 @@ struct AcqArgs {
 };
 void launch_acquire_grad(const PredictGradArgs& a, const AcqArgs& q, hipStream_t s);
 void launch_small_acquire_grad(const SmallPredictGradArgs& a, const AcqArgs& q, hipStream_t s);
+// ---- max-value entropy search over the test points (gprhip_acquire_max_value): the same two kernels with the epilogue of
+// mv_math.h -- per test point a = mean_j psi(gamma_j) over the extremes of n drawn paths, with c_mu and c_v; outputs as above
+// (a.dmeans receives c_mu dmeans + c_v dvars, a.dvars is not used).  The variance part is required (a.G / want_var).  The four
+// lanes of a test point take every fourth extreme and join their sums in a fixed order: no atomics, the same bits every run.
+struct MvArgs {
+  int n;                   // 1 .. MV_MAX_EXTREMES (mv_math.h)
+  double s;                // +1: the extremes are maxima, -1: minima
+  double var_floor;
+  const double* extremes;  // [n] (device)
+  double* values;          // out [rows], or null
+};
+void launch_max_value_grad(const PredictGradArgs& a, const MvArgs& mv, hipStream_t s);
+void launch_small_max_value_grad(const SmallPredictGradArgs& a, const MvArgs& mv, hipStream_t s);
 // the k largest of values[0 .. rows) (acquire.hip): value descending, the lower index first among equal values, NaN never;
 // out = [k] indices as doubles (-1 where fewer than k qualify) | [k] values | [k][D] rows of grads (grads null: not written)
 constexpr int ACQ_MAX_TOP_K = 64;           // GPRHIP_MAX_TOP_K

@@ -27,16 +27,26 @@ constexpr int PG_ROWS = 64;  // test points per workgroup
 // KS4 = ceil(d / 4) k-steps of the distance product, DT = ceil(d / 16) tiles of point dimensions, VAR: the variance part
 // The plain kernel and the one with the criterion epilogue of gprhip_acquire compile the same body text (predict_grad_body.inc,
 // included as small.hip includes its bodies): up to the epilogue they are the same instructions.  ACQ: a.dmeans receives
-// c_mu dmeans + c_v dvars, q.values the criterion; a.dvars is not used.
+// c_mu dmeans + c_v dvars, q.values the criterion; a.dvars is not used.  MV: the same with the coefficients of max-value entropy
+// search (mv.values the criterion).
 template <int KS4, int DT, bool VAR>
 __global__ __launch_bounds__(256) void predict_grad_kernel(PredictGradArgs a) {
-  constexpr bool ACQ = false;
+  constexpr bool ACQ = false, MV = false;
   const AcqArgs q{};
+  const MvArgs mv{};
 #include "predict_grad_body.inc"
 }
 template <int KS4, int DT, bool VAR>
 __global__ __launch_bounds__(256) void acquire_grad_kernel(PredictGradArgs a, AcqArgs q) {
-  constexpr bool ACQ = true;
+  constexpr bool ACQ = true, MV = false;
+  const MvArgs mv{};
+#include "predict_grad_body.inc"
+}
+// MV: the epilogue of gprhip_acquire_max_value (mv_math.h) in place of the criterion of gprhip_acquire; it needs the variance part
+template <int KS4, int DT>
+__global__ __launch_bounds__(256) void max_value_grad_kernel(PredictGradArgs a, MvArgs mv) {
+  constexpr bool ACQ = false, MV = true, VAR = true;
+  const AcqArgs q{};
 #include "predict_grad_body.inc"
 }
 
@@ -58,14 +68,23 @@ void launch_one_acq(const PredictGradArgs& a, const AcqArgs& q, hipStream_t s) {
 // DT: padded point dimension of the direct-difference covariance (d <= DT)
 template <int DT>
 __global__ __launch_bounds__(256) void small_predict_grad_kernel(SmallPredictGradArgs a) {
-  constexpr bool ACQ = false, REFINE = false;
+  constexpr bool ACQ = false, MV = false, REFINE = false;
   const AcqArgs q{};
+  const MvArgs mv{};
   const SmallRefineArgs rf{};
 #include "small_predict_grad_body.inc"
 }
 template <int DT>
 __global__ __launch_bounds__(256) void small_acquire_grad_kernel(SmallPredictGradArgs a, AcqArgs q) {
-  constexpr bool ACQ = true, REFINE = false;
+  constexpr bool ACQ = true, MV = false, REFINE = false;
+  const MvArgs mv{};
+  const SmallRefineArgs rf{};
+#include "small_predict_grad_body.inc"
+}
+template <int DT>
+__global__ __launch_bounds__(256) void small_max_value_grad_kernel(SmallPredictGradArgs a, MvArgs mv) {
+  constexpr bool ACQ = false, MV = true, REFINE = false;
+  const AcqArgs q{};
   const SmallRefineArgs rf{};
 #include "small_predict_grad_body.inc"
 }
@@ -82,6 +101,9 @@ void small_pg_attrs() {
     set(reinterpret_cast<const void*>(&small_acquire_grad_kernel<4>), small_pg_lds(4));
     set(reinterpret_cast<const void*>(&small_acquire_grad_kernel<8>), small_pg_lds(8));
     set(reinterpret_cast<const void*>(&small_acquire_grad_kernel<16>), small_pg_lds(16));
+    set(reinterpret_cast<const void*>(&small_max_value_grad_kernel<4>), small_pg_lds(4));
+    set(reinterpret_cast<const void*>(&small_max_value_grad_kernel<8>), small_pg_lds(8));
+    set(reinterpret_cast<const void*>(&small_max_value_grad_kernel<16>), small_pg_lds(16));
   });
 }
 
@@ -150,6 +172,47 @@ void launch_small_acquire_grad(const SmallPredictGradArgs& a, const AcqArgs& q, 
   auto go = [&](auto dt) {
     constexpr int DT = decltype(dt)::value;
     hipLaunchKernelGGL((small_acquire_grad_kernel<DT>), dim3((a.rows + SRB - 1) / SRB), dim3(256), small_pg_lds(DT), s, a, q);
+  };
+  if (a.d <= 4) go(std::integral_constant<int, 4>{});
+  else if (a.d <= 8) go(std::integral_constant<int, 8>{});
+  else go(std::integral_constant<int, 16>{});
+  GPR_HIP(hipGetLastError());
+}
+
+static void check_mv_args(const MvArgs& mv, bool with_var) {
+  if (mv.n < 1 || mv.n > MV_MAX_EXTREMES || !mv.extremes || !with_var) {
+    set_error("gprhip: the max-value epilogue takes 1 .. 64 extremes and the variance part");
+    throw HipFail{ST_BAD_ARG};
+  }
+}
+
+void launch_max_value_grad(const PredictGradArgs& a, const MvArgs& mv, hipStream_t s) {
+  if (a.rows <= 0) return;
+  if (a.d > 64) {
+    set_error("gprhip: the prediction gradient takes at most 64 point dimensions");
+    throw HipFail{ST_BAD_ARG};
+  }
+  check_mv_args(mv, a.G != nullptr);
+  const dim3 grid((a.rows + PG_ROWS - 1) / PG_ROWS);
+  if (a.d <= 4) hipLaunchKernelGGL((max_value_grad_kernel<1, 1>), grid, dim3(256), 0, s, a, mv);
+  else if (a.d <= 8) hipLaunchKernelGGL((max_value_grad_kernel<2, 1>), grid, dim3(256), 0, s, a, mv);
+  else if (a.d <= 16) hipLaunchKernelGGL((max_value_grad_kernel<4, 1>), grid, dim3(256), 0, s, a, mv);
+  else if (a.d <= 32) hipLaunchKernelGGL((max_value_grad_kernel<8, 2>), grid, dim3(256), 0, s, a, mv);
+  else hipLaunchKernelGGL((max_value_grad_kernel<16, 4>), grid, dim3(256), 0, s, a, mv);
+  GPR_HIP(hipGetLastError());
+}
+
+void launch_small_max_value_grad(const SmallPredictGradArgs& a, const MvArgs& mv, hipStream_t s) {
+  if (a.rows <= 0) return;
+  if (a.m > SM || a.d > 16) {
+    set_error("gprhip: the one-kernel prediction gradient takes at most 64 inducing points of at most 16 dimensions");
+    throw HipFail{ST_BAD_ARG};
+  }
+  check_mv_args(mv, a.want_var != 0);
+  small_pg_attrs();
+  auto go = [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    hipLaunchKernelGGL((small_max_value_grad_kernel<DT>), dim3((a.rows + SRB - 1) / SRB), dim3(256), small_pg_lds(DT), s, a, mv);
   };
   if (a.d <= 4) go(std::integral_constant<int, 4>{});
   else if (a.d <= 8) go(std::integral_constant<int, 8>{});

@@ -99,18 +99,37 @@
     if (VAR && a.vars) a.vars[prow] = (a.sf2 - rsv) + a.add;
   }
   const double inv_ell2 = -2.0 * a.inv_ell2_05;
-  if constexpr (ACQ) {
+  if constexpr (ACQ || MV) {
     // the criterion of test point l15 from its mean and variance (all four lanes of a point alike); without the variance
     // part it is the bound with kappa = 0
     AcqPoint c;
-    if constexpr (VAR) {
-      c = acq_point(q.kind, q.s, q.best, q.xi, q.kappa, q.var_floor, rsm, (a.sf2 - rsv) + a.add);
+    double* cvalues;
+    if constexpr (MV) {
+      // max-value entropy search (mv_math.h): lane lq of the point's four takes the extremes lq, lq + 4, ..., and the partial
+      // sums are joined as rsm and rsv were -- a fixed order
+      const double pvar = (a.sf2 - rsv) + a.add;
+      const bool clamped = !(pvar >= mv.var_floor);
+      const double v = clamped ? mv.var_floor : pvar, sigma = sqrt(v);
+      MvSums t = mv_accumulate(mv.extremes, mv.n, lq, 4, mv.s, rsm, sigma);
+      t.psi += __shfl_xor(t.psi, 16);
+      t.psi += __shfl_xor(t.psi, 32);
+      t.dpsi += __shfl_xor(t.dpsi, 16);
+      t.dpsi += __shfl_xor(t.dpsi, 32);
+      t.gdpsi += __shfl_xor(t.gdpsi, 16);
+      t.gdpsi += __shfl_xor(t.gdpsi, 32);
+      c = mv_finish(t, mv.n, mv.s, sigma, v, clamped);
+      cvalues = mv.values;
     } else {
-      c.a = q.s * rsm;
-      c.cmu = q.s;
-      c.cv = 0.0;
+      if constexpr (VAR) {
+        c = acq_point(q.kind, q.s, q.best, q.xi, q.kappa, q.var_floor, rsm, (a.sf2 - rsv) + a.add);
+      } else {
+        c.a = q.s * rsm;
+        c.cmu = q.s;
+        c.cv = 0.0;
+      }
+      cvalues = q.values;
     }
-    if (lq == 0 && live_r && q.values) q.values[prow] = c.a;
+    if (lq == 0 && live_r && cvalues) cvalues[prow] = c.a;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int orow = row0 + lq + 4 * r;

@@ -20,7 +20,8 @@ namespace {
 
 template <int DT>
 __global__ __launch_bounds__(256) void small_refine_kernel(SmallPredictGradArgs a, AcqArgs q, SmallRefineArgs rf) {
-  constexpr bool ACQ = true, REFINE = true;
+  constexpr bool ACQ = true, MV = false, REFINE = true;
+  const MvArgs mv{};
 #include "small_predict_grad_body.inc"
 }
 

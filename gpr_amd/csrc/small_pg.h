@@ -1,10 +1,11 @@
 // What the kernels that compile small_predict_grad_body.inc share (predict_grad.hip: small_predict_grad_kernel and
-// small_acquire_grad_kernel; refine.hip: small_refine_kernel): the LDS shapes, the 64 x 64 products on
+// small_acquire_grad_kernel, small_max_value_grad_kernel; refine.hip: small_refine_kernel): the LDS shapes, the 64 x 64 products on
 // v_mfma_f64_16x16x4_f64, and the refinement step of gprhip_acquire_refine on the body's lane layout.
 #pragma once
 #include "kernels.h"
 #include "exp_fast.h"
 #include "acq_math.h"
+#include "mv_math.h"
 #include "refine_step.h"
 
 namespace gprhip {

@@ -449,7 +449,14 @@ def _make_variant(spec, variational, functor, cov_kind="FITC"):
             raise TypeError("Acquisition.calc: a trained model (the object of Trained.calc) is needed")
         return _problem_of(trained, inputs).acquire(inputs.points, kind, **kw)
 
-    Eval.Acquisition = SimpleNamespace(calc=acquisition_calc)
+    def acquisition_calc_max_value(trained, inputs, extremes, **kw):
+        """Max-value entropy search over the test inputs from the extremes of drawn paths (gprhip_acquire_max_value through
+        Problem.acquire_max_value, whose keyword arguments and result these are)."""
+        if not isinstance(trained, _Trained):
+            raise TypeError("Acquisition.calc_max_value: a trained model (the object of Trained.calc) is needed")
+        return _problem_of(trained, inputs).acquire_max_value(inputs.points, extremes, **kw)
+
+    Eval.Acquisition = SimpleNamespace(calc=acquisition_calc, calc_max_value=acquisition_calc_max_value)
 
     # ---- new observations folded into the device state without a refit (gprhip_observe, gprhip_posterior_save / _restore
     # through Problem.observe: an extension beyond the reference's implemented surface, whose objects are immutable).

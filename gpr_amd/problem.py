@@ -336,6 +336,104 @@ class Problem:
             out.update(top_index=top_index, top_values=top_values, top_dvalues=top_dvalues)
         return out
 
+    def acquire_max_value(self, test_inputs, extremes, *, maximise, var_floor=None, want=("values", "dvalues"), top_k=0,
+                          out_device_ptrs=None, nt=None):
+        """Max-value entropy search over candidate points (gprhip_acquire_max_value): how much observing a candidate tells
+        about the value of the optimum, "larger is better".  extremes: the extreme values e_j of f on 1 .. 64 drawn paths
+        (host numbers) -- maxima when `maximise`, else minima; `sample_paths_refine` reports the objective s f, so e_j is s
+        times its best value of draw j (`max_value_search` does all of it).  The criterion sees the latent variance
+        max(variance, var_floor), default 1e-10 sf2.  `want`, top_k, the returned dict and out_device_ptrs / nt as `acquire`.
+        `acquire_refine` does not take this criterion."""
+        want = tuple(want)
+        unknown = [w for w in want if w not in self.ACQUIRE_OUTPUTS]
+        if unknown:
+            raise ValueError("acquire_max_value: unknown outputs %s" % unknown)
+        ext = np.ascontiguousarray(extremes, dtype=np.float64)
+        if ext.ndim != 1:
+            raise ValueError("acquire_max_value: extremes is a vector")
+        if var_floor is None:
+            if getattr(self, "_log_sf2", None) is None:
+                raise ValueError("acquire_max_value: var_floor is needed (this object has not seen the model state's log_sf2)")
+            var_floor = 1e-10 * float(np.exp(self._log_sf2))
+        top_k = int(top_k)
+        out = {}
+        kk = max(top_k, 1)
+        top_index = np.full(kk, -1, dtype=np.int64)
+        top_values = np.full(kk, np.nan, dtype=np.float64)
+        top_dvalues = np.full((self.D, kk), np.nan, dtype=np.float64, order="F")
+        tops = ((top_index.ctypes.data_as(C.POINTER(C.c_int64)), _f64_ptr(top_values), _f64_ptr(top_dvalues)) if top_k > 0
+                else (None, None, None))
+        null = C.c_void_p(None)
+        if out_device_ptrs is not None:
+            if nt is None:
+                raise ValueError("acquire_max_value: device buffers need nt")
+            ptrs = {w: (C.c_void_p(int(out_device_ptrs[w])) if w in want else null) for w in self.ACQUIRE_OUTPUTS}
+            xt_ptr, on_device = C.c_void_p(int(test_inputs)), 1
+            nt = int(nt)
+        else:
+            xt = np.asfortranarray(test_inputs, dtype=np.float64)
+            if xt.ndim != 2 or xt.shape[0] != self.D:
+                raise ValueError("acquire_max_value: expected test inputs of shape (%d, nt)" % self.D)
+            nt = xt.shape[1]
+            for w in want:
+                out[w] = (np.full((self.D, nt), np.nan, dtype=np.float64, order="F") if w == "dvalues"
+                          else np.empty(nt, dtype=np.float64))
+            ptrs = {w: (C.c_void_p(out[w].ctypes.data) if w in out else null) for w in self.ACQUIRE_OUTPUTS}
+            xt_ptr, on_device = C.c_void_p(xt.ctypes.data), 0
+        _lib.check(self._lib.gprhip_acquire_max_value(self._handle(), _f64_ptr(ext) if ext.size else None, int(ext.size),
+                                                      int(bool(maximise)), float(var_floor), xt_ptr, self.D, nt, ptrs["values"],
+                                                      ptrs["dvalues"], self.D, ptrs["means"], ptrs["variances"], top_k, *tops,
+                                                      on_device))
+        if top_k > 0:
+            out.update(top_index=top_index, top_values=top_values, top_dvalues=top_dvalues)
+        return out
+
+    def max_value_search(self, z, lower, upper, grid, top_k=4, refine_options=None, *, maximise=True, var_floor=None,
+                         want=("values", "dvalues"), acquire_top_k=0):
+        """Max-value entropy search end to end, host level.  z: m x nd standard normal draws (1 <= nd <= 64); grid: D x nt
+        candidates inside the box [lower, upper].  In this order: `sample_paths` on the grid with the best top_k points per
+        draw; `sample_paths_refine` from those winners (refine_options: its keyword arguments max_evals, step0, ...); per
+        draw the best refined objective o_j; the extremes e_j = s o_j (the refinement reports the objective s f, s = +1 if
+        maximise else -1); `acquire_max_value` over the grid (want, acquire_top_k: its want and top_k).  Returns its dict
+        plus extremes [nd] and extreme_x (D x nd, where each was found)."""
+        z = np.asfortranarray(z, dtype=np.float64)
+        if z.ndim != 2:
+            raise ValueError("max_value_search: expected z of shape (%d, nd)" % self.m)
+        nd = z.shape[1]
+        top_k = int(top_k)
+        if top_k < 1:
+            raise ValueError("max_value_search: top_k starts per draw, at least 1")
+        grid = np.asfortranarray(grid, dtype=np.float64)
+        tops = self.sample_paths(grid, z, maximise=maximise, top_k=top_k, want_samples=False)
+        idx = tops["top_index"]                       # top_k x nd
+        draw_of, cols = [], []
+        for j in range(nd):
+            for i in idx[:, j]:
+                if i >= 0:
+                    draw_of.append(j)
+                    cols.append(int(i))
+        if sorted(set(draw_of)) != list(range(nd)):
+            raise ValueError("max_value_search: a draw has no finite sample on the grid")
+        draw_of = np.asarray(draw_of, dtype=np.int32)
+        ref = self.sample_paths_refine(grid[:, cols], z, draw_of, lower=lower, upper=upper, maximise=maximise,
+                                       want=("x", "values"), **(refine_options or {}))
+        extremes, where = self._extremes_of_refined(ref["values"], draw_of, nd, maximise)
+        out = self.acquire_max_value(grid, extremes, maximise=maximise, var_floor=var_floor, want=want, top_k=acquire_top_k)
+        out.update(extremes=extremes, extreme_x=np.asfortranarray(ref["x"][:, where]))
+        return out
+
+    @staticmethod
+    def _extremes_of_refined(objective, draw_of, nd, maximise):
+        """Per draw the best (largest) refined objective o_j -- the first among equal ones -- as the extreme e_j = s o_j of f,
+        and the start that reached it."""
+        objective = np.asarray(objective, dtype=np.float64)
+        s = 1.0 if maximise else -1.0
+        where = np.empty(nd, dtype=np.int64)
+        for j in range(nd):
+            mine = np.flatnonzero(np.asarray(draw_of) == j)
+            where[j] = mine[np.argmax(objective[mine])]
+        return s * objective[where], where
+
     REFINE_OUTPUTS = ("x", "values", "dvalues", "evals", "accepted", "status", "trace")
 
     def acquire_refine(self, starts, kind, *, lower, upper, maximise, scale=None, best=0.0, xi=0.0, kappa=0.0, var_floor=None,

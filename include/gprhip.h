@@ -421,6 +421,39 @@ int gprhip_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const doubl
                    double* values, double* dvalues, int64_t ldg, double* means, double* variances, int top_k,
                    int64_t* top_index, double* top_values, double* top_dvalues, int on_device);
 
+/* Max-value entropy search over candidate points (MES, Wang & Jegelka 2017), with its gradient and the best top_k candidates:
+ * how much observing a candidate tells about the VALUE of the optimum, from the extreme values of drawn sample paths -- the
+ * second consumer, after Thompson sampling, of what gprhip_sample_paths_refine produces (an extension beyond the reference's
+ * implemented surface).  "Larger is better", as every criterion of gprhip_acquire.  With mu_r / sigma2_r the mean and the LATENT
+ * variance of gprhip_predict_input_grad at candidate r (predictive = 0: sigma2 is not added),
+ *   s = +1 if maximise else -1,  v = max(sigma2_r, var_floor),  sigma = sqrt(v),
+ *   e_j, j < n_extremes: the extreme value of f on drawn path j -- its maximum when maximising, else its minimum,
+ *   gamma_j = s (e_j - mu_r) / sigma,  lambda = phi / Phi,
+ *   psi(gamma)  = gamma lambda(gamma) / 2 - log Phi(gamma)       (> 0, decreasing)
+ *   psi'(gamma) = -(lambda / 2) (1 + gamma (gamma + lambda))
+ *   a    = (1 / S) sum_j psi(gamma_j)
+ *   c_mu = da/dmu     = (1 / S) sum_j psi'(gamma_j) (-s / sigma)
+ *   c_v  = da/dsigma2 = (1 / S) sum_j psi'(gamma_j) (-gamma_j / (2 v)),  0 where the variance was clamped
+ * values[r] = a, dvalues[:, r] = c_mu dmeans[:, r] + c_v dvariances[:, r].  gamma_j < 0 (a drawn extreme on the wrong side of
+ * the mean at the candidate) is legal and accurate: nothing cancels (gpr_amd/csrc/mv_math.h), and the results keep their
+ * relative accuracy down to the subnormal range; |gamma| beyond 1e130 overflows.  The sums over j run in a fixed order, without
+ * atomics: two runs give the same bits.  gprhip_sample_paths_refine reports the objective s f: e_j = s times its best value
+ * of draw j.
+ * extremes: HOST, always (n_extremes doubles).  Every other buffer, on_device, ld / ldg, means / variances and the top_k outputs
+ * are those of gprhip_acquire, word for word.
+ * GPRHIP_EBADARG: n_extremes outside 1 .. GPRHIP_MAX_EXTREMES, extremes NULL, a non-finite extreme, var_floor not positive and
+ * finite, top_k outside 0 .. GPRHIP_MAX_TOP_K, top_k > 0 without top_index, nothing requested, bad ld / ldg.
+ * State and limits: as gprhip_acquire with a criterion that needs the variance -- GPRHIP_ESTATE without a completed evaluation
+ * or a loaded predictor, on a loaded predictor without factors, and after gprhip_eval_targets; fp64 problems, one device, no
+ * multiscales, at most 64 point dimensions on the kernel side.  A refused call enqueues nothing and leaves the state valid; the
+ * call never changes the predictor state.  gprhip_acquire_refine does not take this criterion.
+ * Stage timers: those of gprhip_predict_input_grad, and per chunk "acq_select". */
+#define GPRHIP_MAX_EXTREMES 64
+int gprhip_acquire_max_value(gprhip_problem* p, const double* extremes /* HOST always */, int n_extremes, int maximise,
+                             double var_floor, const double* test_inputs, int64_t ld, int64_t nt, double* values,
+                             double* dvalues, int64_t ldg, double* means, double* variances, int top_k, int64_t* top_index,
+                             double* top_values, double* top_dvalues, int on_device);
+
 /* Refines candidates of an acquisition criterion on the device: projected gradient ascent with Armijo backtracking from ns
  * starting points inside a box, every start on its own -- what follows gprhip_acquire's top_k when the maximiser is wanted and
  * not the best grid point (an extension beyond the reference's implemented surface).  The criterion is any gprhip_acquisition,

@@ -742,6 +742,20 @@ struct Make_deriv {
                              k ? a.top_values.data() : nullptr, k ? a.top_dvalues.data() : nullptr, 0));
         return a;
       }
+      // Max-value entropy search over the test inputs from the extreme values of 1 .. GPRHIP_MAX_EXTREMES drawn paths
+      // (gprhip_acquire_max_value): maxima when `maximise`, else minima; the outputs as calc's.
+      static Acquired_t calc_max_value(const Trained_t& trained, const Inputs_t& in, const Vec& extremes, bool maximise,
+                                       double var_floor, int top_k = 0) {
+        Problem& p = problem_for(trained, in, "Acquisition.calc_max_value");
+        const int k = top_k > 0 ? top_k : 0;
+        Acquired_t a{Vec((size_t)in.points->cols), Mat(in.points->rows, in.points->cols), std::vector<int64_t>((size_t)k, -1),
+                     Vec((size_t)k), Mat(in.points->rows, k > 0 ? k : 1)};
+        check(gprhip_acquire_max_value(p.get(), extremes.empty() ? nullptr : extremes.data(), (int)extremes.size(), maximise ? 1 : 0,
+                                       var_floor, in.points->data(), in.points->rows, in.points->cols, a.values.data(),
+                                       a.dvalues.data(), in.points->rows, nullptr, nullptr, top_k, k ? a.top_index.data() : nullptr,
+                                       k ? a.top_values.data() : nullptr, k ? a.top_dvalues.data() : nullptr, 0));
+        return a;
+      }
       // The starts (D x ns, in.points) refined inside the box [lower, upper] by projected gradient ascent with Armijo
       // backtracking (gprhip_acquire_refine); scale: nullptr for all ones.  status holds GPRHIP_REFINE_ST_* per start.
       static Refined_t refine(const Trained_t& trained, const Inputs_t& in, const gprhip_acquisition& acq,
