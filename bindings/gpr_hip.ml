@@ -63,6 +63,10 @@ external acquire_max_value : problem -> vec -> bool -> float -> mat -> vec optio
    upper) -> starts -> x_out (D x ns) -> values (ns) *)
 external acquire_refine : problem -> vec -> vec -> mat -> mat -> mat -> vec -> unit
   = "gprhip_ml_acquire_refine_bc" "gprhip_ml_acquire_refine"
+(* the same for max-value entropy search (gprhip_acquire_max_value_refine): extremes -> maximise -> var_floor -> options (as
+   acquire_refine) -> box (D x 2) -> starts (D x ns) -> x_out (D x ns) -> values (ns) *)
+external acquire_max_value_refine : problem -> vec -> bool -> float -> vec -> mat -> mat -> mat -> vec -> unit
+  = "gprhip_ml_acquire_max_value_refine_bc" "gprhip_ml_acquire_max_value_refine"
 (* posterior sample paths (gprhip_sample_paths): z (m x ns normal draws) -> points -> eps (nt x ns, or None: the path part
    alone) -> samples (nt x ns) *)
 external sample_paths : problem -> mat -> mat -> mat option -> mat -> unit = "gprhip_ml_sample_paths"

@@ -270,6 +270,50 @@ CAMLprim value gprhip_ml_acquire_refine_bc(value* argv, int argn) {
   return gprhip_ml_acquire_refine(argv[0], argv[1], argv[2], argv[3], argv[4], argv[5], argv[6]);
 }
 
+/* external acquire_max_value_refine : problem -> vec -> bool -> float -> vec -> mat -> mat -> mat -> vec -> unit
+ *   refines the starts (D x ns) of max-value entropy search inside a box (gprhip_acquire_max_value_refine): extremes ->
+ *   maximise -> var_floor as acquire_max_value, options, box, x_out and values as acquire_refine */
+CAMLprim value gprhip_ml_acquire_max_value_refine(value prob, value extremes, value maximise, value var_floor, value options,
+                                                  value box, value starts, value x_out, value values) {
+  CAMLparam5(prob, extremes, maximise, var_floor, options);
+  CAMLxparam4(box, starts, x_out, values);
+  struct caml_ba_array* ba = Caml_ba_array_val(starts);
+  gprhip_problem* p = Problem_val(prob);
+  const double* x = (const double*)ba->data;
+  int64_t ld = ba->dim[0], ns = ba->dim[1];
+  const double* e = (const double*)Caml_ba_data_val(extremes);
+  int n = (int)Caml_ba_array_val(extremes)->dim[0], s = Bool_val(maximise);
+  double floor = Double_val(var_floor);
+  const double* o = (const double*)Caml_ba_data_val(options);
+  const double* b = (const double*)Caml_ba_data_val(box);
+  double* xo = (double*)Caml_ba_data_val(x_out);
+  double* a = (double*)Caml_ba_data_val(values);
+  gprhip_refine_options opt;
+  int status;
+  if (Caml_ba_array_val(options)->dim[0] != 6) caml_invalid_argument("Gpr_hip.acquire_max_value_refine: six options");
+  if (Caml_ba_array_val(box)->dim[0] != ld || Caml_ba_array_val(box)->dim[1] != 2)
+    caml_invalid_argument("Gpr_hip.acquire_max_value_refine: the box is D x 2");
+  if (Caml_ba_array_val(x_out)->dim[0] != ld || Caml_ba_array_val(x_out)->dim[1] != ns ||
+      Caml_ba_array_val(values)->dim[0] != ns)
+    caml_invalid_argument("Gpr_hip.acquire_max_value_refine: x_out is D x ns, values ns");
+  opt.max_evals = (int)o[0];
+  opt.step0 = o[1];
+  opt.c1 = o[2];
+  opt.shrink = o[3];
+  opt.grow = o[4];
+  opt.xtol = o[5];
+  caml_release_runtime_system();
+  status = gprhip_acquire_max_value_refine(p, e, n, s, floor, &opt, b, b + ld, NULL, x, ld, ns, xo, ld, a, NULL, ld, NULL, NULL,
+                                           NULL, NULL, 0);
+  caml_acquire_runtime_system();
+  check(status);
+  CAMLreturn(Val_unit);
+}
+CAMLprim value gprhip_ml_acquire_max_value_refine_bc(value* argv, int argn) {
+  (void)argn;
+  return gprhip_ml_acquire_max_value_refine(argv[0], argv[1], argv[2], argv[3], argv[4], argv[5], argv[6], argv[7], argv[8]);
+}
+
 /* external sample_paths : problem -> z:mat -> points:mat -> eps:mat option -> samples:mat -> unit
  *   posterior sample paths at the points (nt x ns): column j is the draw fixed by column j of z (m x ns standard normal
  *   draws); with eps (nt x ns) the independent residual part is added, without it the path part alone is returned */

@@ -157,6 +157,9 @@ SIGNATURES = {
                                            _vp, _vp, C.c_int, C.POINTER(C.c_int64), _dp, _dp, C.c_int]),
     "gprhip_acquire_refine": (C.c_int, [_vp, C.POINTER(Acquisition), C.POINTER(RefineOptions), _dp, _dp, _dp, _vp, C.c_int64, C.c_int64,
                                         _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int]),
+    "gprhip_acquire_max_value_refine": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_double, C.POINTER(RefineOptions), _dp, _dp, _dp, _vp,
+                                                  C.c_int64, C.c_int64, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp,
+                                                  C.c_int]),
     "gprhip_sample_paths": (C.c_int, [_vp, _dp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int, _vp, C.c_int64,
                                       C.c_int, C.c_int, C.POINTER(C.c_int64), _dp, _dp, C.c_int]),
     "gprhip_sample_paths_refine": (C.c_int, [_vp, _dp, C.c_int64, C.c_int, C.c_int, C.POINTER(RefineOptions), _dp, _dp, _dp, _vp,

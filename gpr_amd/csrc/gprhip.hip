@@ -2274,6 +2274,19 @@ AcqArgs acq_args(const gprhip_acquisition* acq) {
   return q;
 }
 
+// the extremes of a max-value call to the device (p->mv_extremes through the pinned mirror p->mv_host), once the call can no
+// longer be refused
+void mv_upload(gprhip_problem* p, MvArgs* mv, const double* host_extremes) {
+  if (!p->mv_extremes) {
+    p->mv_extremes = p->alloc<double>(GPRHIP_MAX_EXTREMES);
+    GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->mv_host), GPRHIP_MAX_EXTREMES * sizeof(double), hipHostMallocDefault));
+  }
+  // (every earlier call has synchronised the stream before it returned: the mirror is free)
+  std::copy(host_extremes, host_extremes + mv->n, p->mv_host);
+  GPR_HIP(hipMemcpyAsync(p->mv_extremes, p->mv_host, (size_t)mv->n * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  mv->extremes = p->mv_extremes;
+}
+
 // gprhip_acquire: the chunk loop of do_predict_input_grad with the criterion epilogue of the two kernels -- one value vector and
 // one gradient matrix instead of two --, and the best top_k candidates selected on the device chunk by chunk (acquire.hip),
 // the chunks' lists merged here with the same rule: value descending, the lower index first among equal values.
@@ -2290,16 +2303,7 @@ void acquire_walk(gprhip_problem* p, const char* fn, bool want_var, double add, 
   const bool want_grad = dvalues || (top_k > 0 && top_dvalues);
   const bool stage_grad = want_grad && !(on_device && dvalues);  // the gradient of a chunk stays in the library's staging
   const PgPlan plan = pg_prepare(p, fn, nt, want_var, stage_grad);
-  if (mv) {
-    if (!p->mv_extremes) {
-      p->mv_extremes = p->alloc<double>(GPRHIP_MAX_EXTREMES);
-      GPR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->mv_host), GPRHIP_MAX_EXTREMES * sizeof(double), hipHostMallocDefault));
-    }
-    // (every earlier call has synchronised the stream before it returned: the mirror is free)
-    std::copy(host_extremes, host_extremes + mv->n, p->mv_host);
-    GPR_HIP(hipMemcpyAsync(p->mv_extremes, p->mv_host, (size_t)mv->n * sizeof(double), hipMemcpyHostToDevice, s));
-    mv->extremes = p->mv_extremes;
-  }
+  if (mv) mv_upload(p, mv, host_extremes);
   if (top_k > 0 && !p->acq_scratch) {
     p->acq_scratch = p->alloc<char>(acq_select_scratch_bytes());
     p->acq_out = p->alloc<double>((int64_t)ACQ_MAX_TOP_K * (D + 2));
@@ -2480,13 +2484,14 @@ void refine_copy_out(gprhip_problem* p, const RefineStepArgs& st, const RefineWo
 //     on the device;
 //   * every other shape: the loop runs here (refine_host_loop).  State and trial points stay in device buffers, an evaluation
 //     is the chunk walk of gprhip_acquire on them.
+// The criterion is acq or, where mv is not null (acq is then null), max-value entropy search over host_extremes
+// (gprhip_acquire_max_value_refine): the latent variance, always needed; the extremes are uploaded as in acquire_walk.
 // The caller has checked the arguments and the model state; hs: the starts on the host, [ns][D], finite.
-void do_acquire_refine(gprhip_problem* p, const gprhip_acquisition* acq, const gprhip_refine_options* opt, const double* lower,
-                       const double* upper, const double* scale, const double* starts, std::vector<double>& hs, int64_t ns,
-                       double* x_out, int64_t ldx, double* values, double* dvalues, int64_t ldg, int* evals, int* accepted,
-                       int* status, double* trace, int on_device) {
-  const char* const fn = "gprhip_acquire_refine";
-  const bool want_var = acq_wants_var(acq);
+void do_acquire_refine(gprhip_problem* p, const char* fn, const gprhip_acquisition* acq, MvArgs* mv, const double* host_extremes,
+                       const gprhip_refine_options* opt, const double* lower, const double* upper, const double* scale,
+                       const double* starts, std::vector<double>& hs, int64_t ns, double* x_out, int64_t ldx, double* values,
+                       double* dvalues, int64_t ldg, int* evals, int* accepted, int* status, double* trace, int on_device) {
+  const bool want_var = mv ? true : acq_wants_var(acq);
   GPR_HIP(hipSetDevice(p->device));
   hipStream_t s = p->stream;
   const int D = p->D;
@@ -2495,8 +2500,9 @@ void do_acquire_refine(gprhip_problem* p, const gprhip_acquisition* acq, const g
   const PgPlan plan = pg_prepare(p, fn, ns, want_var, false, true, p->rf_len < w.len ? w.len * 8 : 0);
   refine_work(p, w, lower, upper, scale, trace, on_device, true);
   RefineStepArgs st = refine_step_args(p, w, scale != nullptr, refine_opts(opt));
-  AcqArgs q = acq_args(acq);
-  const double add = acq->predictive ? p->h.sigma2 : 0.0;
+  AcqArgs q = mv ? AcqArgs{} : acq_args(acq);
+  const double add = (!mv && acq->predictive) ? p->h.sigma2 : 0.0;
+  if (mv) mv_upload(p, mv, host_extremes);
   if (small) {
     const bool direct = on_device != 0;  // the kernel reads and writes the caller's device buffers
     if (direct) refine_state_in_place(st, x_out, values, dvalues, evals, accepted, status);
@@ -2510,15 +2516,17 @@ void do_acquire_refine(gprhip_problem* p, const gprhip_acquisition* acq, const g
     rf.evals = evals ? st.evals : nullptr; rf.accepted = accepted ? st.accepted : nullptr;
     rf.status = status ? st.status : nullptr; rf.trace = w.trace_dev;
     tstart(p, "rf_small");
-    launch_small_refine(a, q, rf, s);
+    if (mv) launch_small_max_value_refine(a, *mv, rf, s);
+    else launch_small_refine(a, q, rf, s);
     tstop(p);
   } else {
     refine_upload_clipped(p, w, hs, lower, upper);
     if (plan.mats) ensure_predict_m(p);
     q.values = w.AY;
+    if (mv) mv->values = w.AY;
     refine_host_loop(p, plan, st, [&](int, const double* pts, int rows, int rows_p) {
       double* const dsts[2] = {w.GY, nullptr};
-      pg_chunk(p, plan, pts, rows, rows_p, want_var, add, nullptr, nullptr, dsts, &q);
+      pg_chunk(p, plan, pts, rows, rows_p, want_var, add, nullptr, nullptr, dsts, mv ? nullptr : &q, mv);
     });
   }
   refine_copy_out(p, st, w, x_out, ldx, values, dvalues, ldg, evals, accepted, status, trace, on_device);
@@ -4300,8 +4308,40 @@ int gprhip_acquire_refine(gprhip_problem* p, const gprhip_acquisition* acq, cons
     need_posterior_state(p, fn, "predict from", true, acq_wants_var(acq), true,
                          "means and their gradients are available after the next gprhip_eval");
     std::vector<double> hs = refine_starts(fn, p, starts, ld, ns, on_device);
-    do_acquire_refine(p, acq, opt, lower, upper, scale, starts, hs, ns, x_out, ldx, values, dvalues, ldg, evals, accepted, status,
-                      trace, on_device);
+    do_acquire_refine(p, fn, acq, nullptr, nullptr, opt, lower, upper, scale, starts, hs, ns, x_out, ldx, values, dvalues, ldg, evals,
+                      accepted, status, trace, on_device);
+  }, p);
+}
+
+int gprhip_acquire_max_value_refine(gprhip_problem* p, const double* extremes, int n_extremes, int maximise, double var_floor,
+                                    const gprhip_refine_options* opt, const double* lower, const double* upper,
+                                    const double* scale, const double* starts, int64_t ld, int64_t ns, double* x_out,
+                                    int64_t ldx, double* values, double* dvalues, int64_t ldg, int* evals, int* accepted,
+                                    int* status, double* trace, int on_device) {
+  return guarded([&] {
+    const char* const fn = "gprhip_acquire_max_value_refine";
+    auto refuse = [&](const std::string& why) {
+      set_error(std::string(fn) + ": " + why);
+      throw HipFail{ST_BAD_ARG};
+    };
+    if (n_extremes < 1 || n_extremes > GPRHIP_MAX_EXTREMES) refuse("n_extremes must lie in 1 .. GPRHIP_MAX_EXTREMES (64)");
+    if (!extremes) refuse("invalid arguments (extremes is NULL)");
+    for (int j = 0; j < n_extremes; ++j)
+      if (!std::isfinite(extremes[j])) refuse("the extremes must be finite");
+    if (!(var_floor > 0.0) || !std::isfinite(var_floor)) refuse("var_floor must be positive and finite");
+    check_refine_options(fn, opt, ns, x_out || values || dvalues || evals || accepted || status || trace);
+    if (!p || !starts || !lower || !upper) refuse("invalid arguments");
+    if (p->f32) refuse("the prediction gradient is evaluated in fp64 only (GPRHIP_F32_BULK problem)");
+    if (p->d > 64) refuse("at most 64 point dimensions on the kernel side (d)");
+    check_refine_box(fn, p, lower, upper, scale, ld, x_out, ldx, dvalues, ldg, on_device);
+    // the model state before the starts are read back from the device: a refused call enqueues nothing
+    need_posterior_state(p, fn, "predict from", true, true, true,
+                         "means and their gradients are available after the next gprhip_eval");
+    std::vector<double> hs = refine_starts(fn, p, starts, ld, ns, on_device);
+    MvArgs mv;
+    mv.n = n_extremes; mv.s = maximise ? 1.0 : -1.0; mv.var_floor = var_floor; mv.extremes = nullptr; mv.values = nullptr;
+    do_acquire_refine(p, fn, nullptr, &mv, extremes, opt, lower, upper, scale, starts, hs, ns, x_out, ldx, values, dvalues, ldg,
+                      evals, accepted, status, trace, on_device);
   }, p);
 }
 

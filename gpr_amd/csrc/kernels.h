@@ -371,6 +371,9 @@ struct SmallRefineArgs {
 // starts, 64 per workgroup; U^-1, R~^-1, Z - s and t are staged once and the evaluation loop runs inside the kernel.  Of `a`,
 // means / vars / dmeans / dvars / ldg are not used.
 void launch_small_refine(const SmallPredictGradArgs& a, const AcqArgs& q, const SmallRefineArgs& rf, hipStream_t s);
+// the same kernel around the epilogue of launch_small_max_value_grad (gprhip_acquire_max_value_refine): the variance part is
+// required, and the four lanes of a start join their partial sums in the order of the plain kernel
+void launch_small_max_value_refine(const SmallPredictGradArgs& a, const MvArgs& mv, const SmallRefineArgs& rf, hipStream_t s);
 // The step of the library-side loop: refine_step_start (refine_step.h) for every start, one per thread, on the [ns][D] device
 // arrays of RefineStepArgs; *a.active receives the number of starts that go on.  One workgroup, no atomics.
 void launch_refine_step(const RefineStepArgs& a, hipStream_t s);

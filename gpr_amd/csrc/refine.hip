@@ -24,6 +24,13 @@ __global__ __launch_bounds__(256) void small_refine_kernel(SmallPredictGradArgs 
   const MvArgs mv{};
 #include "small_predict_grad_body.inc"
 }
+// the same loop around the epilogue of gprhip_acquire_max_value (mv_math.h): gprhip_acquire_max_value_refine
+template <int DT>
+__global__ __launch_bounds__(256) void small_max_value_refine_kernel(SmallPredictGradArgs a, MvArgs mv, SmallRefineArgs rf) {
+  constexpr bool ACQ = false, MV = true, REFINE = true;
+  const AcqArgs q{};
+#include "small_predict_grad_body.inc"
+}
 
 void small_refine_attrs() {
   static uint64_t done = 0;
@@ -34,6 +41,9 @@ void small_refine_attrs() {
     set(reinterpret_cast<const void*>(&small_refine_kernel<4>), small_pg_lds(4));
     set(reinterpret_cast<const void*>(&small_refine_kernel<8>), small_pg_lds(8));
     set(reinterpret_cast<const void*>(&small_refine_kernel<16>), small_pg_lds(16));
+    set(reinterpret_cast<const void*>(&small_max_value_refine_kernel<4>), small_pg_lds(4));
+    set(reinterpret_cast<const void*>(&small_max_value_refine_kernel<8>), small_pg_lds(8));
+    set(reinterpret_cast<const void*>(&small_max_value_refine_kernel<16>), small_pg_lds(16));
   });
 }
 
@@ -63,6 +73,28 @@ void launch_small_refine(const SmallPredictGradArgs& a, const AcqArgs& q, const 
   auto go = [&](auto dt) {
     constexpr int DT = decltype(dt)::value;
     hipLaunchKernelGGL((small_refine_kernel<DT>), dim3((a.rows + SRB - 1) / SRB), dim3(256), small_pg_lds(DT), s, a, q, rf);
+  };
+  if (a.d <= 4) go(std::integral_constant<int, 4>{});
+  else if (a.d <= 8) go(std::integral_constant<int, 8>{});
+  else go(std::integral_constant<int, 16>{});
+  GPR_HIP(hipGetLastError());
+}
+
+void launch_small_max_value_refine(const SmallPredictGradArgs& a, const MvArgs& mv, const SmallRefineArgs& rf, hipStream_t s) {
+  if (a.rows <= 0) return;
+  if (a.m > SM || a.d > 16) {
+    set_error("gprhip: the one-kernel refinement takes at most 64 inducing points of at most 16 dimensions");
+    throw HipFail{ST_BAD_ARG};
+  }
+  if (mv.n < 1 || mv.n > MV_MAX_EXTREMES || !mv.extremes || !a.want_var) {
+    set_error("gprhip: the max-value epilogue takes 1 .. 64 extremes and the variance part");
+    throw HipFail{ST_BAD_ARG};
+  }
+  small_refine_attrs();
+  auto go = [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    hipLaunchKernelGGL((small_max_value_refine_kernel<DT>), dim3((a.rows + SRB - 1) / SRB), dim3(256), small_pg_lds(DT), s, a, mv,
+                       rf);
   };
   if (a.d <= 4) go(std::integral_constant<int, 4>{});
   else if (a.d <= 8) go(std::integral_constant<int, 8>{});

@@ -343,7 +343,7 @@ class Problem:
         (host numbers) -- maxima when `maximise`, else minima; `sample_paths_refine` reports the objective s f, so e_j is s
         times its best value of draw j (`max_value_search` does all of it).  The criterion sees the latent variance
         max(variance, var_floor), default 1e-10 sf2.  `want`, top_k, the returned dict and out_device_ptrs / nt as `acquire`.
-        `acquire_refine` does not take this criterion."""
+        `acquire_max_value_refine` refines candidates of this criterion."""
         want = tuple(want)
         unknown = [w for w in want if w not in self.ACQUIRE_OUTPUTS]
         if unknown:
@@ -389,13 +389,17 @@ class Problem:
         return out
 
     def max_value_search(self, z, lower, upper, grid, top_k=4, refine_options=None, *, maximise=True, var_floor=None,
-                         want=("values", "dvalues"), acquire_top_k=0):
+                         want=("values", "dvalues"), acquire_top_k=0, refine_top_k=0, candidate_refine_options=None):
         """Max-value entropy search end to end, host level.  z: m x nd standard normal draws (1 <= nd <= 64); grid: D x nt
         candidates inside the box [lower, upper].  In this order: `sample_paths` on the grid with the best top_k points per
         draw; `sample_paths_refine` from those winners (refine_options: its keyword arguments max_evals, step0, ...); per
         draw the best refined objective o_j; the extremes e_j = s o_j (the refinement reports the objective s f, s = +1 if
         maximise else -1); `acquire_max_value` over the grid (want, acquire_top_k: its want and top_k).  Returns its dict
-        plus extremes [nd] and extreme_x (D x nd, where each was found)."""
+        plus extremes [nd] and extreme_x (D x nd, where each was found).
+        refine_top_k = k > 0: `acquire_max_value` runs with top_k = max(acquire_top_k, k), and its best k grid candidates are
+        refined inside the box by `acquire_max_value_refine` (candidate_refine_options: its keyword arguments max_evals,
+        step0, ...); the dict gains refined_x (D x k'), refined_values [k'], refined_dvalues (D x k') and refined_status
+        [k'], k' <= k the candidates that qualified, best grid candidate first."""
         z = np.asfortranarray(z, dtype=np.float64)
         if z.ndim != 2:
             raise ValueError("max_value_search: expected z of shape (%d, nd)" % self.m)
@@ -418,8 +422,21 @@ class Problem:
         ref = self.sample_paths_refine(grid[:, cols], z, draw_of, lower=lower, upper=upper, maximise=maximise,
                                        want=("x", "values"), **(refine_options or {}))
         extremes, where = self._extremes_of_refined(ref["values"], draw_of, nd, maximise)
-        out = self.acquire_max_value(grid, extremes, maximise=maximise, var_floor=var_floor, want=want, top_k=acquire_top_k)
+        refine_top_k = int(refine_top_k)
+        if refine_top_k < 0:
+            raise ValueError("max_value_search: refine_top_k is a count, at least 0")
+        out = self.acquire_max_value(grid, extremes, maximise=maximise, var_floor=var_floor, want=want,
+                                     top_k=max(acquire_top_k, refine_top_k))
         out.update(extremes=extremes, extreme_x=np.asfortranarray(ref["x"][:, where]))
+        if refine_top_k > 0:
+            best = [int(i) for i in out["top_index"][:refine_top_k] if i >= 0]
+            if not best:
+                raise ValueError("max_value_search: no grid candidate has a finite criterion")
+            fine = self.acquire_max_value_refine(grid[:, best], extremes, lower=lower, upper=upper, maximise=maximise,
+                                                 var_floor=var_floor, want=("x", "values", "dvalues", "status"),
+                                                 **(candidate_refine_options or {}))
+            out.update(refined_x=fine["x"], refined_values=fine["values"], refined_dvalues=fine["dvalues"],
+                       refined_status=fine["status"])
         return out
 
     @staticmethod
@@ -496,6 +513,61 @@ class Problem:
         _lib.check(self._lib.gprhip_acquire_refine(self._handle(), C.byref(acq), C.byref(opt), *bptr, st_ptr, self.D, ns,
                                                    ptrs["x"], self.D, ptrs["values"], ptrs["dvalues"], self.D, ptrs["evals"],
                                                    ptrs["accepted"], ptrs["status"], ptrs["trace"], on_device))
+        return out
+
+    def acquire_max_value_refine(self, starts, extremes, *, lower, upper, maximise, scale=None, var_floor=None, max_evals=50,
+                                 step0=0.1, c1=1e-4, shrink=0.5, grow=2.0, xtol=1e-8,
+                                 want=("x", "values", "dvalues", "evals", "accepted", "status"), out_device_ptrs=None, ns=None):
+        """Refines candidates of max-value entropy search on the device (gprhip_acquire_max_value_refine): the rule of
+        `acquire_refine` on the criterion of `acquire_max_value` -- extremes, maximise and var_floor as there (host numbers,
+        the latent variance).  Box, scale, the rule's constants, `want`, the outputs and out_device_ptrs / ns as
+        `acquire_refine`."""
+        want = tuple(want)
+        unknown = [w for w in want if w not in self.REFINE_OUTPUTS]
+        if unknown:
+            raise ValueError("acquire_max_value_refine: unknown outputs %s" % unknown)
+        ext = np.ascontiguousarray(extremes, dtype=np.float64)
+        if ext.ndim != 1:
+            raise ValueError("acquire_max_value_refine: extremes is a vector")
+        if var_floor is None:
+            if getattr(self, "_log_sf2", None) is None:
+                raise ValueError("acquire_max_value_refine: var_floor is needed (this object has not seen the model state's "
+                                 "log_sf2)")
+            var_floor = 1e-10 * float(np.exp(self._log_sf2))
+        opt = _lib.RefineOptions(int(max_evals), float(step0), float(c1), float(shrink), float(grow), float(xtol))
+        box = [np.ascontiguousarray(b, dtype=np.float64) for b in (lower, upper)]
+        if scale is not None:
+            box.append(np.ascontiguousarray(scale, dtype=np.float64))
+        if any(b.shape != (self.D,) for b in box):
+            raise ValueError("acquire_max_value_refine: lower, upper and scale take %d entries each" % self.D)
+        bptr = [_f64_ptr(b) for b in box] + ([None] if scale is None else [])
+        null = C.c_void_p(None)
+        out = {}
+        if out_device_ptrs is not None:
+            if ns is None:
+                raise ValueError("acquire_max_value_refine: device buffers need ns")
+            ptrs = {w: (C.c_void_p(int(out_device_ptrs[w])) if w in want else null) for w in self.REFINE_OUTPUTS}
+            st_ptr, on_device, ns = C.c_void_p(int(starts)), 1, int(ns)
+        else:
+            xs = np.asfortranarray(starts, dtype=np.float64)
+            if xs.ndim != 2 or xs.shape[0] != self.D:
+                raise ValueError("acquire_max_value_refine: expected starts of shape (%d, ns)" % self.D)
+            ns = xs.shape[1]
+            for w in want:
+                if w in ("x", "dvalues"):
+                    out[w] = np.full((self.D, ns), np.nan, dtype=np.float64, order="F")
+                elif w == "values":
+                    out[w] = np.full(ns, np.nan, dtype=np.float64)
+                elif w == "trace":
+                    out[w] = np.full((ns, int(max_evals), 2 * self.D + 3), np.nan, dtype=np.float64)
+                else:
+                    out[w] = np.full(ns, -1, dtype=np.int32)
+            ptrs = {w: (C.c_void_p(out[w].ctypes.data) if w in out else null) for w in self.REFINE_OUTPUTS}
+            st_ptr, on_device = C.c_void_p(xs.ctypes.data), 0
+        _lib.check(self._lib.gprhip_acquire_max_value_refine(
+            self._handle(), _f64_ptr(ext) if ext.size else None, int(ext.size), int(bool(maximise)), float(var_floor),
+            C.byref(opt), *bptr, st_ptr, self.D, ns, ptrs["x"], self.D, ptrs["values"], ptrs["dvalues"], self.D, ptrs["evals"],
+            ptrs["accepted"], ptrs["status"], ptrs["trace"], on_device))
         return out
 
     def sample_paths_refine(self, starts, z, draw_of, *, lower, upper, maximise=True, scale=None, max_evals=50, step0=0.1,

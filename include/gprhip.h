@@ -446,7 +446,7 @@ int gprhip_acquire(gprhip_problem* p, const gprhip_acquisition* acq, const doubl
  * State and limits: as gprhip_acquire with a criterion that needs the variance -- GPRHIP_ESTATE without a completed evaluation
  * or a loaded predictor, on a loaded predictor without factors, and after gprhip_eval_targets; fp64 problems, one device, no
  * multiscales, at most 64 point dimensions on the kernel side.  A refused call enqueues nothing and leaves the state valid; the
- * call never changes the predictor state.  gprhip_acquire_refine does not take this criterion.
+ * call never changes the predictor state.  gprhip_acquire_max_value_refine refines candidates of this criterion.
  * Stage timers: those of gprhip_predict_input_grad, and per chunk "acq_select". */
 #define GPRHIP_MAX_EXTREMES 64
 int gprhip_acquire_max_value(gprhip_problem* p, const double* extremes /* HOST always */, int n_extremes, int maximise,
@@ -504,6 +504,36 @@ int gprhip_acquire_refine(gprhip_problem* p, const gprhip_acquisition* acq, cons
                           const double* upper, const double* scale, const double* starts, int64_t ld, int64_t ns, double* x_out,
                           int64_t ldx, double* values, double* dvalues, int64_t ldg, int* evals, int* accepted, int* status,
                           double* trace, int on_device);
+
+/* Refines candidates of max-value entropy search on the device: the maximiser of the information criterion, what follows
+ * gprhip_acquire_max_value's top_k when it is wanted and not the best grid point (an extension beyond the reference's
+ * implemented surface).  The criterion, its value a and gradient g, the LATENT variance, var_floor and the extremes (HOST
+ * always, n_extremes doubles, 1 .. GPRHIP_MAX_EXTREMES, finite) are those of gprhip_acquire_max_value, word for word;
+ * gprhip_acquisition has no kind for it, the extremes do not fit its layout.
+ * The rule (steps 1 - 4), gprhip_refine_options, the status codes, lower / upper / scale (HOST always, D doubles each; scale
+ * == NULL means all ones), every output and its layout in either mode, on_device, GPRHIP_REFINE_MAX_STARTS and
+ * GPRHIP_REFINE_MAX_EVALS are those of gprhip_acquire_refine, word for word -- the trace is [ns][max_evals][2 D + 3] doubles,
+ * evaluation j of a start writes record j = (y, g_y, a_y, alpha, accepted as 0 / 1), record 0 is the clipped start with
+ * alpha = 0 and accepted = 1, and records after the last evaluation are left untouched.
+ * Two routes, one rule, as gprhip_acquire_refine.  At most 64 inducing points of at most 16 dimensions without a projection:
+ * ONE persistent kernel, the evaluator of gprhip_acquire_max_value's one-kernel path inside the loop; the four lanes of a
+ * start take every fourth extreme and join their sums in the order of that kernel.  Every other shape: the loop runs in the
+ * library on device buffers, an evaluation is gprhip_acquire_max_value's chunk walk -- the very kernels, the same bits at the
+ * same point --, a step kernel follows, and one integer comes back per evaluation.  A start's result does not depend on the
+ * other starts; no atomics: two runs give the same bits.
+ * GPRHIP_EBADARG: what gprhip_acquire_max_value refuses of n_extremes, extremes and var_floor; what gprhip_acquire_refine
+ * refuses of the options, the box, scale, the starts, ns, the outputs and ld / ldx / ldg.  State and limits: as
+ * gprhip_acquire_max_value (GPRHIP_ESTATE under the same conditions; the variance part is always needed).  New buffers are
+ * checked against the free device memory first (GPRHIP_EOOM).  A refused call enqueues nothing; the call never changes the
+ * predictor state.
+ * Limits: those of gprhip_acquire_refine; the latent-variance form of the criterion only.
+ * Stage timers: "rf_small" (the persistent kernel); on the other route those of gprhip_acquire_max_value per evaluation and
+ * "rf_step". */
+int gprhip_acquire_max_value_refine(gprhip_problem* p, const double* extremes /* HOST always */, int n_extremes, int maximise,
+                                    double var_floor, const gprhip_refine_options* opt, const double* lower, const double* upper,
+                                    const double* scale, const double* starts, int64_t ld, int64_t ns, double* x_out,
+                                    int64_t ldx, double* values, double* dvalues, int64_t ldg, int* evals, int* accepted,
+                                    int* status, double* trace, int on_device);
 
 /* Posterior sample paths over test points, with the best top_k points of every draw -- Thompson sampling, batch selection by
  * independent draws, posterior pictures over a grid (an extension beyond the reference's implemented surface; its Cov_sampler
@@ -638,8 +668,8 @@ int gprhip_load_predictor(gprhip_problem* p, const gprhip_hypers* h, const doubl
  *              dl2 = -1/2 |rho|^2,  rho = what the QR leaves of eta  (|eta|^2 + |b|^2 = |b'|^2 + |rho|^2)
  *            Without targets it holds dl1 alone.
  * Afterwards every posterior call reads the conditioned model: gprhip_predict, gprhip_predict_input_grad, gprhip_acquire,
- * gprhip_acquire_refine, gprhip_sample_paths, gprhip_sample_paths_refine, gprhip_covariances, gprhip_train_stats,
- * gprhip_co_variance_coeffs -- a model file saved afterwards holds the conditioned predictor.  The matrix M of
+ * gprhip_acquire_refine, gprhip_acquire_max_value_refine, gprhip_sample_paths, gprhip_sample_paths_refine,
+ * gprhip_covariances, gprhip_train_stats, gprhip_co_variance_coeffs -- a model file saved afterwards holds the conditioned predictor.  The matrix M of
  * gprhip_predict_input_grad and the weights of gprhip_sample_paths are formed again at their next use (debug names "pg_m" and
  * "sp_a" are GPRHIP_ESTATE until then; "w_mat" is scratch of the update).  The condition estimate stays: K_m is unchanged.
  * WHAT DOES NOT CHANGE: the resident training set (inputs, targets, V and the validity of reuse_v).  The next gprhip_eval

@@ -772,6 +772,24 @@ struct Make_deriv {
                                     r.status.data(), nullptr, 0));
         return r;
       }
+      // The same for max-value entropy search (gprhip_acquire_max_value_refine): the criterion of calc_max_value -- extremes,
+      // maximise, var_floor -- climbed by the rule of refine.
+      static Refined_t refine_max_value(const Trained_t& trained, const Inputs_t& in, const Vec& extremes, bool maximise,
+                                        double var_floor, const gprhip_refine_options& opt, const Vec& lower, const Vec& upper,
+                                        const Vec* scale = nullptr) {
+        Problem& p = problem_for(trained, in, "Acquisition.refine_max_value");
+        const size_t D = (size_t)in.points->rows, ns = (size_t)in.points->cols;
+        if (lower.size() != D || upper.size() != D || (scale && scale->size() != D))
+          throw std::invalid_argument("Acquisition.refine_max_value: lower, upper and scale take D entries each");
+        Refined_t r{Mat(in.points->rows, in.points->cols), Vec(ns), Mat(in.points->rows, in.points->cols), std::vector<int>(ns),
+                    std::vector<int>(ns), std::vector<int>(ns)};
+        check(gprhip_acquire_max_value_refine(p.get(), extremes.empty() ? nullptr : extremes.data(), (int)extremes.size(),
+                                              maximise ? 1 : 0, var_floor, &opt, lower.data(), upper.data(),
+                                              scale ? scale->data() : nullptr, in.points->data(), in.points->rows, in.points->cols,
+                                              r.x.data(), in.points->rows, r.values.data(), r.dvalues.data(), in.points->rows,
+                                              r.evals.data(), r.accepted.data(), r.status.data(), nullptr, 0));
+        return r;
+      }
     };
     // New observations folded into the device state of a trained model or a model without a refit (gprhip_observe,
     // gprhip_posterior_save / _restore: an extension beyond the reference's implemented surface, whose objects are immutable).
